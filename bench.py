@@ -2,6 +2,7 @@
 """bench.py -- frustums/sec of the hot path's training step (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--cfg car|people|refine|sunrgbd] [--precision split|f32|bf16]
+                    [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N
 
 One step = the reference's train-loop body on one batch (train/train_net_det.py:120-133): forward of PointNetDet in train
@@ -10,16 +11,20 @@ Adam update, on a synthetic batch already resident in HBM (default: KITTI-car-sh
 points, strides (0.25,0.5,1,2) -> L = (280,140,70,35)); weak scaling.  The step is captured into hipGraph(s) and replayed
 (no host work in the timed region besides the replays and, for N > 1, the collective calls); --eager disables it.
 
-Timing: W warm-up steps, then EXACTLY K steps bracketed by barrier + synchronize; when K steps take less than --min-time
-seconds (default 1 s) the K-step window is repeated back to back (`rounds` of K steps each, all inside ONE bracket) and
-ms_per_step is the mean over rounds * K steps -- a 40 ms window says little about a GPU that clocks by power budget.
+Timing: W warm-up steps, then EXACTLY K steps bracketed by barrier + synchronize, ms_per_step = their wall time / K.  A replay
+holds two whole steps (double-buffered workspaces): with N = 1 an odd K ends with one replay of a graph of the last step alone;
+the N > 1 forms round K (and W) up to whole replays.  --min-time S > 0: when K steps take less than S seconds, the K-step window
+is repeated back to back (`rounds` of K steps each, all inside ONE bracket) and ms_per_step is the mean over rounds * K steps.
 
-Rank 0 prints ONE JSON line with the contract fields plus
+Rank 0 prints ONE JSON line with the contract fields (metric, value, unit, higher_is_better, dtype, ms_per_step, ...).
+--dump-outputs DIR: after the timed steps, what the last one handed its caller -- losses, metrics, raw logits, the parameters
+after its optimiser step, its gradients, the BatchNorm running statistics -- as DIR/<name>.npy (float32 / float64, <= 64 MB).
+--full adds (N=1) measurements of their own behind the headline:
   roofline     -- the top-time kernel family of the step, timed LIVE (HIP events around its C-ABI entry point, on the stream
                   it is launched on, eager launches of the same step), with a `kernels` table for every entry point
   configs      -- short timed windows (>= 0.35 s each) of the other BASELINE.json configurations: people, refine, the
-                  SUN-RGBD variant and the bf16 throughput mode of the car config (N=1, default car / split invocation only)
-  cpu_baseline -- the CPU oracle (oracle/det_ref.py + oracle/qdp_ref.c) timed on the host cores, N=1 only, <= ~30 s
+                  SUN-RGBD variant and the bf16 throughput mode of the car config (default car / split invocation only)
+  cpu_baseline -- the CPU oracle (oracle/det_ref.py + oracle/qdp_ref.c) timed on the host cores, <= ~30 s
 """
 import argparse
 import ctypes
@@ -59,7 +64,12 @@ def parse():
     ap.add_argument("--batch", type=int, default=32, help="frustums per GPU")
     ap.add_argument("--npoint", type=int, default=None)
     ap.add_argument("--cfg", choices=sorted(CFGS), default="car")
-    ap.add_argument("--min-time", type=float, default=1.0, help="minimum length of the timed region in seconds")
+    ap.add_argument("--min-time", type=float, default=0.0,
+                    help="minimum length of the timed region in seconds (repeats the K-step window); 0: exactly --steps steps")
+    ap.add_argument("--full", action="store_true",
+                    help="also the roofline / kernel table, the other configurations and the CPU baseline (runs of their own)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy")
     ap.add_argument("--eager", action="store_true", help="no hipGraph capture")
     ap.add_argument("--no-optim", action="store_true", help="time forward+backward(+all-reduce) only")
     ap.add_argument("--no-overlap", action="store_true", help="N > 1: one all-reduce after the whole backward")
@@ -507,6 +517,8 @@ def measure(a, cfg_name, prec, steps, warmup, min_time, dev, rank, world, batch=
     pf_point = os.environ.get("FCN_PF_POINT", "fcn_fwd")
     resident = data
     spg = max(2, 2 * (int(os.environ.get("FCN_STEPS_PER_GRAPH", "2")) // 2))      # whole steps per captured graph (even)
+    # the losses / metrics of the step run or captured last: after the timed window, those of its last step (--dump-outputs)
+    last = {}
 
     def fwd_bwd():
         data = sets[kstep[0] % 2] if sets else resident          # this step's batch, and the next one's (the other buffer)
@@ -518,7 +530,8 @@ def measure(a, cfg_name, prec, steps, warmup, min_time, dev, rank, world, batch=
             model.next_batch = nxt                    # forward() starts the prefetch beside the ConvFeatNet forward
             if sets:
                 model.next_batch_build = lambda: builder.launch(t_raw, out=nxt)
-        losses, _ = model(data)
+        losses, metrics = model(data)
+        last.update(losses=losses, metrics=metrics)
         if prefetch and pf_point != "fcn_fwd":
             # the next step's batch (the same resident synthetic batch): its batch-only front -- grouping, entry rows, tile lists,
             # input moments -- runs on a side branch beside this step's backward, as a loader prefetches; the work stays INSIDE the
@@ -530,6 +543,7 @@ def measure(a, cfg_name, prec, steps, warmup, min_time, dev, rank, world, batch=
     use_graph = not a.eager
     graphs = None
     split_scales = None
+    capture_tail = None
     side = torch.cuda.Stream()
     side.wait_stream(torch.cuda.current_stream())
     with torch.cuda.stream(side):
@@ -579,7 +593,8 @@ def measure(a, cfg_name, prec, steps, warmup, min_time, dev, rank, world, batch=
                             state.adam_step()
                     if prefetch:
                         model.next_batch = data
-                    losses, _ = model(data)
+                    losses, metrics = model(data)
+                    last.update(losses=losses, metrics=metrics)
                     lt = losses["total_loss"]
                     pending = model.take_split()
                     lt.backward(gradient=unit_grad(lt.device))
@@ -631,7 +646,8 @@ def measure(a, cfg_name, prec, steps, warmup, min_time, dev, rank, world, batch=
                             state.adam_step()
                         if prefetch:
                             model.next_batch = data
-                        losses, _ = model(data)
+                        losses, metrics = model(data)
+                        last.update(losses=losses, metrics=metrics)
                         loss = losses["total_loss"]
                         pending = model.take_split()
                         loss.backward(gradient=unit_grad(loss.device))
@@ -663,11 +679,25 @@ def measure(a, cfg_name, prec, steps, warmup, min_time, dev, rank, world, batch=
                 glist.append(g)
                 steps_per_graph = spg if prefetch else 1
                 graphs = (tuple(glist),)
+                if world == 1:
+                    def capture_tail(r):
+                        # the last r steps of a window that is not a whole number of replays, as a graph of their own: it takes
+                        # over from the whole-step graph exactly as that graph's next replay would, but leaves the workspace sets
+                        # out of turn for it -- so it is replayed once, as the last thing of the timed window
+                        gt = torch.cuda.CUDAGraph()
+                        with torch.cuda.graph(gt, capture_error_mode=mode):
+                            model.feat_net.adopt_prefetch()
+                            for _ in range(r):
+                                fwd_bwd()
+                                if optim:
+                                    opt_step()
+                        return gt
         except Exception as e:  # noqa
             if rank == 0:
                 print("[bench] hipGraph capture failed (%s: %s); falling back to eager launches" %
                       (type(e).__name__, e), file=sys.stderr)
             graphs = None
+            capture_tail = None
             overlap = False
             captured_comm = False
             late = False
@@ -722,24 +752,33 @@ def measure(a, cfg_name, prec, steps, warmup, min_time, dev, rank, world, batch=
     for _ in range(even(warmup)):
         step()
     torch.cuda.synchronize()
-    # length of one K-step window -> number of rounds for a timed region of at least min_time seconds
-    t0 = time.perf_counter()
-    for _ in range(even(steps)):
-        step()
-    torch.cuda.synchronize()
-    probe = time.perf_counter() - t0
-    rounds = max(1, int(np.ceil(min_time / max(probe, 1e-6))))
-    if world > 1:
-        rt = torch.tensor([rounds], device=dev)
-        torch.distributed.all_reduce(rt, op=torch.distributed.ReduceOp.MAX)
-        rounds = int(rt.item())
-        torch.distributed.barrier()
+    rounds = 1
+    if min_time > 0:
+        # length of one K-step window -> number of rounds for a timed region of at least min_time seconds
+        t0 = time.perf_counter()
+        for _ in range(even(steps)):
+            step()
+        torch.cuda.synchronize()
+        probe = time.perf_counter() - t0
+        rounds = max(1, int(np.ceil(min_time / max(probe, 1e-6))))
+        if world > 1:
+            rt = torch.tensor([rounds], device=dev)
+            torch.distributed.all_reduce(rt, op=torch.distributed.ReduceOp.MAX)
+            rounds = int(rt.item())
+            torch.distributed.barrier()
+    nstep = even(rounds * steps)
+    tail = None
+    if nstep != rounds * steps and capture_tail is not None:
+        nstep = rounds * steps
+        tail = capture_tail(nstep % steps_per_graph)
     torch.cuda.synchronize()
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     t0 = time.perf_counter()
     e0.record()
-    for _ in range(even(rounds * steps)):
+    for _ in range(nstep - nstep % steps_per_graph if tail is not None else nstep):
         step()
+    if tail is not None:
+        tail.replay()
     state.wait_allreduce()                           # (N > 1: the last step's collectives belong to the timed region)
     e1.record()
     torch.cuda.synchronize()
@@ -751,7 +790,6 @@ def measure(a, cfg_name, prec, steps, warmup, min_time, dev, rank, world, batch=
     if world > 1:
         torch.distributed.all_reduce(tt, op=torch.distributed.ReduceOp.MAX)
     wall = float(tt.item())
-    nstep = even(rounds * steps)
     if captured_comm and graphs is not None and optim:    # the last captured step's gradients: its successor's head would have applied them
         model._cn_pool.before_pack = None
         state.adam_step()
@@ -794,8 +832,8 @@ def measure(a, cfg_name, prec, steps, warmup, min_time, dev, rank, world, batch=
         torch.distributed.barrier()
     return {"captured_comm": captured_comm, "rehearse": rehearse, "model": model, "state": state, "data": data, "graphs": graphs, "overlap": overlap, "optim": optim, "comm": comm,
             "rounds": rounds, "nstep": nstep, "wall": wall, "ms_per_step": wall * 1e3 / nstep,
-            "gpu_event_ms_per_step": e0.elapsed_time(e1) / nstep, "final_loss": float(loss.item()),
-            "steps_per_graph": steps_per_graph, "prefetch": prefetch, "late_adam": bool(late),
+            "gpu_event_ms_per_step": e0.elapsed_time(e1) / nstep, "final_loss": float(last["losses"]["total_loss"].item()),
+            "losses": last["losses"], "metrics": last["metrics"], "steps_per_graph": steps_per_graph, "prefetch": prefetch, "late_adam": bool(late),
             "batch": batch, "npoint": npoint, "Ls": Ls}
 
 
@@ -1052,6 +1090,46 @@ def other_configs(a, dev, min_time=0.3, car_flops=None):
     return out
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def step_outputs(m):
+    """What the last timed step hands its caller, by name: losses, metrics, the raw logits, and the model after its optimiser
+    step -- parameters, their gradients, the BatchNorm running statistics (model order, flattened)."""
+    model = m["model"]
+    out = {"loss_" + k: v for k, v in m["losses"].items()}
+    out.update(("metric_" + k, v) for k, v in m["metrics"].items())
+    out["cls_logits"], out["reg_logits"] = model.last_logits
+    params = [p for _, p in model.named_parameters()]
+    out["params"] = torch.cat([p.detach().reshape(-1) for p in params])
+    out["grads"] = torch.cat([p.grad.reshape(-1) for p in params])
+    out["bn_running_stats"] = torch.cat([b.reshape(-1) for n, b in model.named_buffers() if "running_" in n])
+    return out
+
+
+def dump_outputs(dirname, outputs, limit=DUMP_LIMIT_BYTES):
+    """Writes every tensor / array of `outputs` as dirname/<name>.npy, float64 as float64, everything else as float32.  Past
+    `limit` bytes in all, every array of more than 4096 elements is cut to the same share of its elements: a sample drawn with a
+    fixed seed (sorted flat indices), so two runs sample alike."""
+    arrs = {}
+    for k, v in outputs.items():
+        v = v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v)
+        arrs[k] = np.ascontiguousarray(v, dtype=np.float64 if v.dtype == np.float64 else np.float32)
+    big = [k for k, v in arrs.items() if v.size > 4096]
+    small_bytes = sum(v.nbytes for k, v in arrs.items() if k not in big)
+    big_bytes = sum(arrs[k].nbytes for k in big)
+    if small_bytes + big_bytes > limit:
+        share = (limit - small_bytes) / big_bytes
+        for k in big:
+            v = arrs[k].reshape(-1)
+            keep = np.sort(np.random.RandomState(0).choice(v.size, int(v.size * share), replace=False))
+            arrs[k] = v[keep]
+    os.makedirs(dirname, exist_ok=True)
+    for k, v in arrs.items():
+        np.save(os.path.join(dirname, k + ".npy"), v)
+    return sorted(arrs)
+
+
 def main():
     a = parse()
     from frustum_convnet_amd import dist as fdist, precision as fprec
@@ -1090,6 +1168,8 @@ def main():
     model, state, data, graphs, overlap, optim = m["model"], m["state"], m["data"], m["graphs"], m["overlap"], m["optim"]
     rounds, nstep, wall, ms_per_step, final_loss = m["rounds"], m["nstep"], m["wall"], m["ms_per_step"], m["final_loss"]
     gpu_event_ms = m["gpu_event_ms_per_step"]
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, step_outputs(m))      # (before --full's measurements step this model further)
 
     if rank != 0:
         _shutdown_group()
@@ -1145,7 +1225,7 @@ def main():
         if m["comm"]["backend"] == "nccl":
             out["rccl_ranks"] = m["comm"]["ranks"]   # (only a communicator that IS RCCL is reported under that name)
         out["comm"] = m["comm"]
-    if world == 1 and not a.no_roofline:
+    if world == 1 and a.full and not a.no_roofline:
         try:
             model.split_backward = False
             rows, peak_mm, how = kernel_table(model, state, data, optim, prec, graph=not a.eager)
@@ -1179,7 +1259,7 @@ def main():
             car_flops = float(sum(r.get("flops_executed", 0.0) for r in rows)) if a.cfg == "car" else None
         except Exception as e:  # noqa
             out["roofline"] = {"error": "%s: %s" % (type(e).__name__, e)}
-    if world == 1:
+    if world == 1 and a.full:
         # whole-step HBM roofline (BASELINE.json's "HBM roofline %"): fabric bytes of one step from the committed rocprofv3
         # --pmc passes over THIS command and THIS kernel source, divided by the step time measured now.
         st, why = pmc_traffic("step", cfg_name=a.cfg, prec=prec)
@@ -1192,7 +1272,7 @@ def main():
         else:
             out["hbm_roofline"] = {"traffic": None, "note": why}
     rehearsal = m["rehearse"]
-    if world == 1 and not a.no_configs and a.cfg == "car" and prec == "split" and not a.eager and not rehearsal:
+    if world == 1 and a.full and not a.no_configs and a.cfg == "car" and prec == "split" and not a.eager and not rehearsal:
         # the other BASELINE.json configurations, driver-visible in the same line: free the headline model first
         del model, state, data, graphs, m
         torch.cuda.synchronize()
@@ -1212,7 +1292,7 @@ def main():
         torch.cuda.empty_cache()
         out["configs"] = other_configs(a, dev, car_flops=car_flops)
         fprec.set_precision(prec)
-    if world == 1 and not a.no_cpu_baseline:
+    if world == 1 and a.full and not a.no_cpu_baseline:
         try:
             out["cpu_baseline"] = cpu_baseline(a.cpu_baseline_batch, npoint, a.cfg)
         except Exception as e:  # noqa

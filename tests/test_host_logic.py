@@ -370,6 +370,31 @@ def test_bench_gpus_n_never_prints_a_line_for_fewer_ranks(tmp_path):
         assert r.returncode != 0 and '"metric"' not in r.stdout, (gpus, world, r.stdout[-300:], r.stderr[-300:])
 
 
+def test_bench_plain_run_and_output_dump(tmp_path, monkeypatch):
+    """A plain `bench.py --steps K` times exactly K steps (no --min-time repetition) and measures nothing beyond the headline
+    (--full is off); --dump-outputs writes float32 / float64 .npy files and, past the size limit, the same seeded sample every time."""
+    import sys
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "7"])
+    a = bench.parse()
+    assert a.steps == 7 and a.min_time == 0 and not a.full and a.dump_outputs is None
+    outs = {"loss": torch.tensor([2.5]), "params": torch.arange(20000, dtype=torch.float32), "logits": torch.ones(3, 4, dtype=torch.float64),
+            "count": torch.tensor(5, dtype=torch.int64)}
+    names = bench.dump_outputs(str(tmp_path / "a"), outs)
+    got = {n: np.load(str(tmp_path / "a" / (n + ".npy"))) for n in names}
+    assert got["params"].dtype == np.float32 and np.array_equal(got["params"], np.arange(20000, dtype=np.float32))
+    assert got["logits"].dtype == np.float64 and got["logits"].shape == (3, 4)
+    assert got["loss"].dtype == np.float32 and got["count"].dtype == np.float32 and float(got["count"]) == 5.0
+    limit = 40000
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), outs, limit=limit)
+    files = sorted(os.listdir(str(tmp_path / "b")))
+    assert sum(os.path.getsize(str(tmp_path / "b" / f)) for f in files) <= limit + 128 * len(files)      # (+ .npy headers)
+    b, c = (np.load(str(tmp_path / d / "params.npy")) for d in ("b", "c"))
+    assert 0 < b.size < 20000 and np.array_equal(b, c) and np.all(np.diff(b) > 0)
+    assert np.array_equal(np.load(str(tmp_path / "b" / "logits.npy")), np.ones((3, 4)))
+
+
 def test_pmc_traffic_is_keyed_by_configuration(tmp_path, monkeypatch):
     """every non-car bench line printed the CAR configuration's HBM counters.  The record is now keyed by
     configuration and tied to the kernel sources: another configuration, or other sources, give None + the reason (-> `traffic: null`)."""

@@ -8,12 +8,12 @@ CFGS="${TRAFFIC_CFGS:-car people refine sunrgbd}" bash tools/gpu_traffic.sh > $O
 cp $O/pmc_traffic.json $R/profiles/pmc_traffic.json     # (on the box only: lets the bench below print traffic; merged back via gpurun_out)
 cp $O/pmc_traffic.json $O/${T}_pmc_traffic.json; cp $O/pmc_sq_summary.txt $O/${T}_pmc_sq_summary.txt
 cd $R
-echo "== bench car (full, default invocation)"; timeout 600 python bench.py > $O/${T}_bench_car.json 2> $O/${T}_bench_car.err; echo "rc=$?"; tail -1 $O/${T}_bench_car.json | cut -c1-300
+echo "== bench car (--full)"; timeout 600 python bench.py --full > $O/${T}_bench_car.json 2> $O/${T}_bench_car.err; echo "rc=$?"; tail -1 $O/${T}_bench_car.json | cut -c1-300
 for c in people refine sunrgbd; do
-  echo "== bench $c"; timeout 600 python bench.py --cfg $c --steps 100 --warmup 20 --no-cpu-baseline --no-configs > $O/${T}_bench_$c.json 2> $O/${T}_bench_$c.err; echo "rc=$?"; tail -1 $O/${T}_bench_$c.json | cut -c1-200
+  echo "== bench $c"; timeout 600 python bench.py --full --cfg $c --steps 100 --warmup 20 --no-cpu-baseline --no-configs > $O/${T}_bench_$c.json 2> $O/${T}_bench_$c.err; echo "rc=$?"; tail -1 $O/${T}_bench_$c.json | cut -c1-200
 done
 for p in f32 bf16 bf16ops; do
-  echo "== bench car $p"; timeout 600 python bench.py --precision $p --steps 200 --warmup 30 --no-cpu-baseline --no-configs > $O/${T}_bench_car_$p.json 2> $O/${T}_bench_car_$p.err; echo "rc=$?"; tail -1 $O/${T}_bench_car_$p.json | cut -c1-200
+  echo "== bench car $p"; timeout 600 python bench.py --full --precision $p --steps 200 --warmup 30 --no-cpu-baseline --no-configs > $O/${T}_bench_car_$p.json 2> $O/${T}_bench_car_$p.err; echo "rc=$?"; tail -1 $O/${T}_bench_car_$p.json | cut -c1-200
 done
 echo "== phase stamps"; timeout 300 python tools/phase_stamps.py > $O/${T}_phase_stamps.txt 2>&1; tail -9 $O/${T}_phase_stamps.txt
 for c in car sunrgbd; do

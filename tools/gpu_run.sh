@@ -7,7 +7,7 @@
 #   tests[=<pytest args>]                   -m gpu tests (default: the whole suite), summary on stdout
 #   smoke                                   __graft_entry__.smoke()
 #   bench=<name>[,VAR=V...][::<args>]       one bench.py line under the given environment -> <TAG>_bench_<name>.json
-#   full=<name>[,VAR=V...][::<args>]        the same without the --no-* switches (roofline table, configs, CPU baseline)
+#   full=<name>[,VAR=V...][::<args>]        the same with --full instead of the --no-* switches (roofline table, configs, CPU baseline)
 #   ab=<rounds>:<specA>/<specB>[/...][::<args>]   alternating short bench lines of several environments on this one box;
 #                                           spec = <name>[,VAR=V...]  (FCN_LIB_NAME=libfcn_hip_<x>.so selects a tuning build)
 #   prof=<name>[,VAR=V...][::<args>]        rocprofv3 --kernel-trace --stats of a 20-step bench run -> <TAG>_kernel_stats_<name>.csv
@@ -43,7 +43,7 @@ for step in "$@"; do
     smoke)
       echo "== smoke"; timeout 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" 2>&1 | tail -2 ;;
     bench|full)
-      parse "$rest"; sw=$QUICK; [ $kind = full ] && sw=""
+      parse "$rest"; sw=$QUICK; [ $kind = full ] && sw="--full"
       echo "== $kind $NAME [$ENVS] $args"
       env $ENVS timeout 900 python bench.py $sw $args > $O/${T}_bench_$NAME.json 2> $O/${T}_bench_$NAME.err; echo "rc=$? $(line $O/${T}_bench_$NAME.json)" ;;
     ab)
