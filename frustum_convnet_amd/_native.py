@@ -11,6 +11,11 @@ LIB_PATH = os.path.join(_HERE, os.environ.get("FCN_LIB_NAME", "libfcn_hip.so")) 
 
 c_fp = ctypes.c_void_p
 
+# BatchNorm modes of fcn_pn_desc.training / fcn_cn_desc.training (FCN_BN_*)
+BN_RUNNING = 0       # running statistics, no saved state: inference
+BN_TRAIN = 1         # batch statistics + running-stat update, differentiable
+BN_FROZEN = 2        # running statistics, never written, differentiable (frozen-BatchNorm fine-tuning)
+
 
 class PnDesc(ctypes.Structure):
     _fields_ = [("B", ctypes.c_int32), ("N", ctypes.c_int32), ("L", ctypes.c_int32), ("K", ctypes.c_int32),

@@ -14,6 +14,22 @@
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
+// The BatchNorm mode of a descriptor (fcn_pn_desc / fcn_cn_desc .training, FCN_BN_* of fcn_hip.h).  Every launch planner reads it
+// through these three predicates only: a raw truthiness test would count FCN_BN_FROZEN (2) as "batch statistics".
+template <class D> static inline bool bn_mode_valid(const D *d)
+{
+    return d->training == FCN_BN_TRAIN || d->training == FCN_BN_RUNNING || d->training == FCN_BN_FROZEN;
+}
+// batch statistics (and the running-stat update): training mode only
+template <class D> static inline bool uses_batch_stats(const D *d) { return d->training == FCN_BN_TRAIN; }
+// the forward saves what a backward reads (pre-BN activations, arg-max maps, backward images, zeroed backward sums)
+template <class D> static inline bool saves_for_backward(const D *d)
+{
+    return d->training == FCN_BN_TRAIN || d->training == FCN_BN_FROZEN;
+}
+// differentiable with the running statistics: the backward's batch-mean terms vanish
+template <class D> static inline bool frozen_stats(const D *d) { return d->training == FCN_BN_FROZEN; }
+
 #define FCN_CHECK_LAUNCH()                         \
     do {                                           \
         hipError_t e__ = hipGetLastError();        \
@@ -170,7 +186,7 @@ struct FcnBnBwd {
     const double *bstat;       // replica 0 of [sum dz [C], sum dz * xhat [C]]
     int rep_stride;            // doubles between replicas (fcn_rep_sum)
     const float *gamma, *bn;
-    double invM;
+    double invM;               // 1 / M; 0 under frozen statistics (FCN_BN_FROZEN): the two batch-mean terms vanish, dy = c0 * dz
     float *dgamma, *dbeta;     // exported by the workgroup flagged `pub` (fp32), or null
 };
 __device__ __forceinline__ void fcn_bnbwd_coef(const FcnBnBwd &q, int C, int c, float (&cf)[5], bool pub)

@@ -779,6 +779,7 @@ __global__ __launch_bounds__(G * 64 * MW * WNC) void cgk_fwd_pair_kernel(CgLayer
 struct CgBnBwd {
     const double *bstat;       // sum dz [Cs], sum dz*xhat [Cs] (final, replica 0); nullptr: the layer has no BN (heads)
     int rep_stride;            // doubles between replica blocks (the whole bstat arena)
+    int frozen;                // FCN_BN_FROZEN: the forward normalised with the running statistics -- no batch-mean terms
     const float *gamma, *bn;   // bn: (scale, shift, mean, rstd) published by the forward
     double M;
     float *dgamma, *dbeta;     // non-null on the launch that exports them
@@ -791,7 +792,8 @@ __device__ __forceinline__ void cg_bnbwd_coef(const QT &q, int Cs, int c, float 
     const float rstd = q.bn[3 * Cs + c];
     cf[0] = q.gamma[c] * rstd;
     cf[1] = q.bn[2 * Cs + c];
-    const double invM = 1.0 / q.M;                      // (one division; the two per-channel quotients become products)
+    // (one division; the two per-channel quotients become products.  Frozen statistics: 0, so c2 = c3 = 0 and dy = c0 * dz)
+    const double invM = q.frozen ? 0.0 : 1.0 / q.M;
     const double c0 = (double)cf[0];                    // the folded form of fcn_common.h: dy = fma(c0, dz, -fma(c2, y - c1, c3))
     cf[2] = (float)(c0 * (double)rstd * (dg * invM));
     cf[3] = (float)(c0 * (db * invM));
@@ -809,7 +811,7 @@ __device__ __forceinline__ void cg_bnbwd_coef_pre(const QT &q, int Cs, int c, co
     for (int r = 1; r < FCN_CG_REP; ++r) { db += sb[r]; dg += sg[r]; }
     cf[0] = gam * rstd;
     cf[1] = mean;
-    const double invM = 1.0 / q.M;
+    const double invM = q.frozen ? 0.0 : 1.0 / q.M;
     const double c0 = (double)cf[0];
     cf[2] = (float)(c0 * (double)rstd * (dg * invM));
     cf[3] = (float)(c0 * (db * invM));
@@ -1982,7 +1984,7 @@ static void cn_fill_layer(const fcn_cn_desc *d, const fcn_cn_params *p, const Cn
         else {
             S.x = ws->y + O.y[src]; S.bn = ws->bn + O.bn[src]; S.st16 = 1;
             S.Lsrc = P.Lout[src] * (P.dk[src] > 0 ? P.dk[src] : 1);     // a deconv's buffer is (B, L*k, 256)
-            S.stat = d->training ? ws->stat + O.st[src] : nullptr;
+            S.stat = uses_batch_stats(d) ? ws->stat + O.st[src] : nullptr;
             S.gamma = p->gamma[src]; S.beta = p->beta[src]; S.rmean = p->running_mean[src]; S.rvar = p->running_var[src];
             S.nbt = p->num_batches_tracked[src];
             S.M = (double)d->B * P.Lout[src] * (P.dk[src] > 0 ? P.dk[src] : 1);
@@ -2014,10 +2016,10 @@ static int cn_pack(const fcn_cn_desc *d, const fcn_cn_params *p, const CnPlan &P
         t.src[l] = nullptr; t.dst[l] = nullptr; t.pre[l + 1] = t.pre[l]; t.nrow_real[l] = 0;
     }
     t.oh = one_hot; t.oh64 = ws->oh64; t.B = d->B; t.nvec = d->nvec;
-    t.z0 = d->training ? ws->stat : nullptr; t.z1 = d->training ? ws->bstat : nullptr; t.nz = FCN_CG_REP * O.st[P.nl];
+    t.z0 = uses_batch_stats(d) ? ws->stat : nullptr; t.z1 = saves_for_backward(d) ? ws->bstat : nullptr; t.nz = FCN_CG_REP * O.st[P.nl];
     t.enc = ws->wp + O.wp[P.nl];            // second third of the weight arena (fcn_convnet_sizes)
     t.mmf = CN_MM_OF(d->precision, true);
-    t.grd = d->training ? ws->wp + 2 * O.wp[P.nl] : nullptr;      // third third: only a backward reads it
+    t.grd = saves_for_backward(d) ? ws->wp + 2 * O.wp[P.nl] : nullptr;      // third third: only a backward reads it
     t.mmb = CN_MM_OF(d->precision, false);
     hipLaunchKernelGGL(cg_pack_kernel,
                        dim3((unsigned)(((t.grd ? 2 : 1) * (t.pre[CN_NLAYER] / 8) + (int64_t)d->B * OH_PAD + t.nz + 255) / 256)),
@@ -2031,7 +2033,7 @@ static int cn_pack(const fcn_cn_desc *d, const fcn_cn_params *p, const CnPlan &P
 extern "C" int fcn_convnet_pack(const fcn_cn_desc *d, const fcn_cn_params *p, const fcn_cn_ws *ws, const float *one_hot,
                                 void *stream)
 {
-    if (!d || !p || !ws || !ws->wp || !ws->oh64) return FCN_E_BADARG;
+    if (!d || !p || !ws || !ws->wp || !ws->oh64 || !bn_mode_valid(d)) return FCN_E_BADARG;
     if (d->nvec > 0 && !one_hot) return FCN_E_BADARG;
     if (d->nvec > OH_PAD) return FCN_E_LIMIT;
     CnPlan P;
@@ -2060,7 +2062,7 @@ extern "C" int fcn_convnet_forward2(const fcn_cn_desc *d, const fcn_cn_params *p
                                     const float *const feats[FCN_CN_MAXLEV], const float *one_hot, float *logits,
                                     void *stream, void *const *feat_events)
 {
-    if (!d || !p || !ws || !feats || !logits) return FCN_E_BADARG;
+    if (!d || !p || !ws || !feats || !logits || !bn_mode_valid(d)) return FCN_E_BADARG;
     if (!ws->y || !ws->wp || !ws->bn || !ws->stat || !ws->partial || !ws->oh64) return FCN_E_BADARG;
     if (d->nvec > 0 && !one_hot) return FCN_E_BADARG;
     if (d->nvec > OH_PAD) return FCN_E_LIMIT;
@@ -2069,7 +2071,7 @@ extern "C" int fcn_convnet_forward2(const fcn_cn_desc *d, const fcn_cn_params *p
     FCN_TRY(cn_make_plan(d, P));
     CnOffsets O;
     cn_offsets(d, P, O);
-    const int tr = d->training ? 1 : 0;
+    const int tr = uses_batch_stats(d) ? 1 : 0;          // (frozen statistics: no batch sums, no running-stat update)
     if (d->precision < 0 || d->precision > FCN_PREC_BF16_OPS) return FCN_E_BADARG;
     const int mmf = CN_MM_OF(d->precision, true);
     if (!d->prepacked) FCN_TRY(cn_pack(d, p, P, O, ws, one_hot, st));      // (also zeroes ws->stat / ws->bstat)
@@ -2178,7 +2180,7 @@ extern "C" int fcn_convnet_backward(const fcn_cn_desc *d, const fcn_cn_params *p
                                     void *stream, void *stream2, void *const *events)
 {
     if (!d || !p || !ws || !feats || !dlogits || !dfeats || !dW || !dgamma || !dbeta || !dbias) return FCN_E_BADARG;
-    if (!d->training) return FCN_E_BADARG;
+    if (!bn_mode_valid(d) || !saves_for_backward(d)) return FCN_E_BADARG;
     if (!ws->y || !ws->dz || !ws->wp || !ws->bn || !ws->bstat || !ws->coef || !ws->partial) return FCN_E_BADARG;
     // stream2 / events (nlev caller-owned hipEvent_t), optional: the gradient of the widest feature map (dfeats[nlev-1]) is
     // final after the third launch (heads, last deconvolution, last merge).  From there the remaining launches continue
@@ -2212,7 +2214,7 @@ extern "C" int fcn_convnet_backward(const fcn_cn_desc *d, const fcn_cn_params *p
     // data-gradient + weight-gradient roles of layer l (l < 0: none); returns the workgroups in front of the reduce role
     auto make_step = [&](int l, float *pbuf, CgBwdStep &a, CgReduce &own, int &own_blocks) -> int {
         a.ndg = 0; a.w_ns = 0; a.w_ny = 1; a.rows = 2 * KC; a.partial = nullptr; a.dz = nullptr; a.dz16 = 0;
-        a.cb.bstat = nullptr; a.cb.rep_stride = O.st[P.nl]; a.cb.gamma = nullptr; a.cb.bn = nullptr; a.cb.M = 1.0; a.cb.dgamma = nullptr; a.cb.dbeta = nullptr;
+        a.cb.bstat = nullptr; a.cb.rep_stride = O.st[P.nl]; a.cb.frozen = frozen_stats(d) ? 1 : 0; a.cb.gamma = nullptr; a.cb.bn = nullptr; a.cb.M = 1.0; a.cb.dgamma = nullptr; a.cb.dbeta = nullptr;
         CgDgSeg *dgs[CG_NSEG] = {&a.dg[0], &a.dg[1], &a.dg[2], &a.dg[3]};
         for (int s = 0; s < CG_NSEG; ++s) {
             dgs[s]->sg = 0; dgs[s]->segoff = 0; dgs[s]->ysrc = dgs[s]->bnsrc = nullptr; dgs[s]->out = nullptr;

@@ -51,7 +51,8 @@ struct GcArgs {
     GcScale s[GC_MAX_SCALES];
     PackArgs pk[GC_MAX_SCALES];    // conv2 / conv3 weights of every scale -> ws.wenc (packed by the first launch, on the side)
     const float *pc;           // (B,3,N)
-    int B, N, training, use_lds;
+    int B, N, use_lds;
+    int batch_stats;           // 1: BN1 from the batch moments + running-stat update (FCN_BN_TRAIN); 0: running statistics
     float eps, momentum;
     int fold;                  // 1: the entries launch also folds BN1 (scale / shift, running statistics) from the input moments;
                                // 0: data-only front (fcn_pn_group_compact2 phase 1) -- gc_fold_kernel does it later, after the
@@ -80,7 +81,7 @@ __device__ __forceinline__ void gc_fold_bn1(const GcArgs &a, const GcScale &S, c
     const double M = (double)a.B * (double)S.L * (double)S.K;
     for (int c = tid; c < S.C1; c += nthr) {
         double mean, var;
-        if (a.training) {
+        if (a.batch_stats) {
             // (one fp64 division, no software sqrt: this workgroup is the tail of the front every scale waits for)
             const double iM = 1.0 / M;
             const double mx = mo[1] * iM, my = mo[2] * iM, mz = mo[3] * iM;
@@ -380,13 +381,13 @@ extern "C" int fcn_pn_group_compact2(int nscale, const fcn_pn_desc *const *d, co
         K.W2 = p[q]->W[1]; K.W3 = p[q]->W[2]; K.wenc = (s < nscale && phase != 1) ? ws[q]->wenc : nullptr;
         K.C1 = D->C1; K.C2 = D->C2; K.C3 = D->C3; K.precision = D->precision;
         if (!K.W2 || !K.W3 || ((uintptr_t)ws[q]->wenc & 15) || D->precision < 0 || D->precision > FCN_PREC_BF16_OPS) return FCN_E_BADARG;
-        if (!D->training && (!S.rmean || !S.rvar)) return FCN_E_BADARG;
+        if (!bn_mode_valid(D) || (!uses_batch_stats(D) && (!S.rmean || !S.rvar))) return FCN_E_BADARG;
         const size_t need = (size_t)(2 * D->L + 1) * sizeof(int) + (size_t)3 * D->L * sizeof(float);
         if (need > lds) lds = need;
         const int ns_ = (D->L + GC_WPB - 1) / GC_WPB;
         if (s < nscale && ns_ > maxslice) maxslice = ns_;
     }
-    a.pc = pc; a.B = d[0]->B; a.N = d[0]->N; a.training = d[0]->training ? 1 : 0; a.eps = d[0]->eps; a.momentum = d[0]->momentum;
+    a.pc = pc; a.B = d[0]->B; a.N = d[0]->N; a.batch_stats = uses_batch_stats(d[0]) ? 1 : 0; a.eps = d[0]->eps; a.momentum = d[0]->momentum;
     a.use_lds = (a.N <= GC_LDS_MAX_PTS) ? 1 : 0;
     a.fold = (phase == 3) ? 1 : 0;
     if (lds > 64 * 1024) return FCN_E_LIMIT;

@@ -5,6 +5,8 @@
 //   dbeta = sum_e dz,  dgamma = sum_e dz * xhat
 //   dy[e] = gamma*rstd * (dz[e] - w_e*dbeta/M - w_e*xhat[e]*dgamma/M)      (w_e = multiplicity, M = B*L*K)
 //   dW    = sum_e dy[e] (x) a_prev[e],   G_prev[e] = W^T dy[e]
+//   Frozen statistics (FCN_BN_FROZEN: mean / rstd are the running ones, constants of the batch): dy[e] = gamma*rstd * dz[e] --
+//   the same kernels with 1/M = 0 in the coefficients and the layer-1 finalisation without its db*mu and dg terms
 //
 //   poolbwd        : routes dfeat to the max rows (gmax), dbeta3/dgamma3
 //   dgrad<3>       : builds dy3 while staging (writes it once), G2 = dy3 . W3 on MFMA, ReLU mask from y2,
@@ -801,6 +803,7 @@ struct L1Args {
     const double *mom;
     const float *W1, *gamma, *bn1;
     int C;
+    int frozen;                 // FCN_BN_FROZEN: BN1 normalised with the running statistics (no batch-mean terms)
     double M;
     float *dW1, *dgamma, *dbeta;
 };
@@ -825,7 +828,7 @@ __device__ __forceinline__ void l1_finalize_body(const L1Args &a, const int c)
     for (int j = 0; j < 3; ++j) {
         const double wm2 = w[0] * m2[0][j] + w[1] * m2[1][j] + w[2] * m2[2][j];
         // sum_e w x^ u_j = rstd * M * (W1_c . m2[:,j] - mean * mu_j);  sum_e w u_j = M mu_j
-        const double v = kk * (qu[j] - db * mu[j] - dg * rstd * (wm2 - mean * mu[j]));
+        const double v = a.frozen ? kk * qu[j] : kk * (qu[j] - db * mu[j] - dg * rstd * (wm2 - mean * mu[j]));
         a.dW1[3 * c + j] = (float)v;
     }
     a.dgamma[c] = (float)dg;
@@ -945,6 +948,7 @@ static L1Args make_l1(const fcn_pn_desc *d, const fcn_pn_params *p, const fcn_pn
 {
     L1Args a;
     a.Qr = bsQ; a.rep_stride = brs; a.mom = ws->stat + FCN_STAT_MOM; a.W1 = p->W[0]; a.gamma = p->gamma[0]; a.bn1 = bn1; a.C = d->C1; a.M = M;
+    a.frozen = frozen_stats(d) ? 1 : 0;
     a.dW1 = dW0; a.dgamma = dgamma0; a.dbeta = dbeta0;
     return a;
 }
@@ -1075,7 +1079,7 @@ static int pn_backward_impl(const fcn_pn_desc *d, const fcn_pn_params *p, const 
                             void *const *events, const float *dz3_dense)
 {
     if (!d || !p || !ws || !dfeat || !dW || !dgamma || !dbeta) return FCN_E_BADARG;
-    if (!d->training || !ws->wenc) return FCN_E_BADARG;
+    if (!bn_mode_valid(d) || !saves_for_backward(d) || !ws->wenc) return FCN_E_BADARG;
     if (d->precision < 0 || d->precision > FCN_PREC_BF16_OPS) return FCN_E_BADARG;
     if (ws->partial_both < 0 || ws->partial_both > 2) return FCN_E_BADARG;      // (an uninitialised trailing field must not enable the merged launches)
     hipStream_t st = (hipStream_t)stream;
@@ -1087,6 +1091,7 @@ static int pn_backward_impl(const fcn_pn_desc *d, const fcn_pn_params *p, const 
     if (C1 % 64 || C2 % 64 || C3 % 64 || C1 > MAXC || C2 > MAXC || C3 > MAXC) return FCN_E_BADARG;
     const int cap = L * K;
     const double M = (double)B * (double)L * (double)K;
+    const double invM = frozen_stats(d) ? 0.0 : 1.0 / M;       // (frozen statistics: no batch-mean terms)
     const int tps = (cap + 127) / 128;
     if (ws->nsplit < B * tps) return FCN_E_BADARG;
     const float *bn1 = ws->bn + fcn_bn_off(0, C1, C2);
@@ -1110,7 +1115,7 @@ static int pn_backward_impl(const fcn_pn_desc *d, const fcn_pn_params *p, const 
     g.ent = (const float4 *)ws->ent; g.woff = ws->woff; g.tiles = ws->tiles; g.ewin = ws->ewin; g.L = L; g.cap = cap; g.tps = tps;
     g.ycur = ws->y3; g.amax = ws->amax; g.gmax = ws->gmax; g.dzcur = nullptr;
     g.Wenc = (const u32x4 *)(ws->wenc + 2 * (int64_t)C2 * C1 + (int64_t)C3 * C2);            // G3 (pn_wenc_off(3))
-    g.cb.bstat = bs3; g.cb.rep_stride = brs; g.cb.gamma = p->gamma[2]; g.cb.bn = bn3; g.cb.invM = 1.0 / M; g.cb.dgamma = dgamma[2]; g.cb.dbeta = dbeta[2];
+    g.cb.bstat = bs3; g.cb.rep_stride = brs; g.cb.gamma = p->gamma[2]; g.cb.bn = bn3; g.cb.invM = invM; g.cb.dgamma = dgamma[2]; g.cb.dbeta = dbeta[2];
     g.dybuf = ws->dy3; g.yprev = ws->y2; g.bn_prev = bn2; g.W1 = nullptr; g.dzprev = ws->dz2; g.bstat_prev = bs2;
     g.CRED = C3; g.CPREV = C2;
 #if FCN_XB & 512       // (timing build: the cost of a2 . G instead of dy3 . W3 -- reduction over C2, the A operand read from y2)
@@ -1127,7 +1132,7 @@ static int pn_backward_impl(const fcn_pn_desc *d, const fcn_pn_params *p, const 
     w.ent = (const float4 *)ws->ent; w.woff = ws->woff; w.tiles = ws->tiles; w.L = L; w.cap = cap; w.tps = tps;
     w.partial = ws->partial;
     w.dy = ws->dy3; w.dz = nullptr; w.ycur = nullptr; w.yprev = ws->y2; w.bn_prev = bn2;
-    w.cb.bstat = nullptr; w.cb.rep_stride = brs; w.cb.gamma = nullptr; w.cb.bn = nullptr; w.cb.invM = 1.0 / M; w.cb.dgamma = nullptr; w.cb.dbeta = nullptr;
+    w.cb.bstat = nullptr; w.cb.rep_stride = brs; w.cb.gamma = nullptr; w.cb.bn = nullptr; w.cb.invM = invM; w.cb.dgamma = nullptr; w.cb.dbeta = nullptr;
     w.ewin = nullptr; w.amax = nullptr; w.gmax = nullptr;
     if (!ws->dy3) {        // no dy3 buffer: conv3's weight-gradient GEMM rebuilds dy3 from what the data-gradient GEMM reads
         w.ycur = ws->y3; w.cb.bstat = bs3; w.cb.gamma = p->gamma[2]; w.cb.bn = bn3;

@@ -30,13 +30,13 @@
 // ------------------------------------------------------------------------------------------------
 __global__ void bn1_finalize_kernel(const double *__restrict__ mom, const float *__restrict__ W1,
                                     const float *__restrict__ gamma, const float *__restrict__ beta,
-                                    float *rmean, float *rvar, int64_t *nbt, int C, int training,
+                                    float *rmean, float *rvar, int64_t *nbt, int C, int batch_stats,
                                     float eps, float momentum, double M, float *__restrict__ bn)
 {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= C) return;
     double mean, var;
-    if (training) {
+    if (batch_stats) {
         const double mx = mom[1] / M, my = mom[2] / M, mz = mom[3] / M;
         const double cxx = mom[4] / M - mx * mx, cxy = mom[5] / M - mx * my, cxz = mom[6] / M - mx * mz;
         const double cyy = mom[7] / M - my * my, cyz = mom[8] / M - my * mz, czz = mom[9] / M - mz * mz;
@@ -64,7 +64,7 @@ __global__ void bn1_finalize_kernel(const double *__restrict__ mom, const float 
 
 __global__ void bn_finalize_kernel(const double *__restrict__ stat, int rep_stride, const float *__restrict__ gamma,
                                    const float *__restrict__ beta, float *rmean, float *rvar, int64_t *nbt,
-                                   int C, int training, float eps, float momentum, double M,
+                                   int C, int batch_stats, float eps, float momentum, double M,
                                    float *__restrict__ bn)
 {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
@@ -72,7 +72,7 @@ __global__ void bn_finalize_kernel(const double *__restrict__ stat, int rep_stri
     // (one fp64 division per thread, none per statistic, and no software sqrt: this launch sits between two layers of a
     // latency-bound chain)
     double mean, var;
-    if (training) {
+    if (batch_stats) {
         const double invM = 1.0 / M;
         mean = fcn_rep_sum(stat + c, rep_stride) * invM;
         var = fcn_rep_sum(stat + C + c, rep_stride) * invM - mean * mean;
@@ -163,7 +163,8 @@ struct FwdArgs {
     const u32x4 *Wenc;     // forward image of the conv weight (pn_pack_*): [CIN/32][2][4][COUT]
     int32_t *flags;        // sticky numeric flags (fcn_pn_ws.flags) or nullptr
     float *y;              // (B,cap,COUT)
-    double *stat;          // sum[COUT], sumsq[COUT] or nullptr (eval)
+    double *stat;          // sum[COUT], sumsq[COUT] or nullptr (running statistics)
+    int save_y;            // y is stored even when the max-pool rides in this epilogue (POOL): a backward will read it
     int L, cap, CIN, COUT, tps;
     // MODE 1 with gamma_in set: the BN in front of this conv is FINALISED BY ITS CONSUMER -- every workgroup derives scale /
     // shift in its prologue from the batch sums (training) or the running statistics (eval) instead of waiting for a
@@ -422,7 +423,7 @@ __global__ __launch_bounds__(128 * WN) __attribute__((amdgpu_waves_per_eu(MT == 
     if (FCN_X & 16) { if (acc[0][0][0] == 123.456f) a.y[0] = 0.f; return; }
     bool bad = false;
     // (eval mode with the pooling in this epilogue: nothing reads y afterwards -- the keys carry the pooled values)
-    const bool store_y = !POOL || a.stat != nullptr;
+    const bool store_y = !POOL || a.save_y;
 #if FCN_FWD_EPI_DIRECT      // (tuning builds: one dword per lane straight from the accumulator layout -- the round-2 epilogue)
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt)
@@ -895,7 +896,7 @@ static int launch_fwd_gemm(const FwdArgs &a, int B, int precision, hipStream_t s
 extern "C" int fcn_pn_forward(const fcn_pn_desc *d, const fcn_pn_params *p, const int32_t *cnt,
                               const float *one_hot, const fcn_pn_ws *ws, float *feat, void *stream)
 {
-    if (!d || !p || !ws || !cnt || !feat || !ws->wenc) return FCN_E_BADARG;
+    if (!d || !p || !ws || !cnt || !feat || !ws->wenc || !bn_mode_valid(d)) return FCN_E_BADARG;
     if (d->C1 % 64 || d->C2 % 64 || d->C3 % 64 || d->C1 > MAXC || d->C2 > MAXC) return FCN_E_BADARG;
     if (d->nvec > 0 && !one_hot && !d->nlc) return FCN_E_BADARG;
     if (d->nvec * PW > GT) return FCN_E_LIMIT;
@@ -903,9 +904,10 @@ extern "C" int fcn_pn_forward(const fcn_pn_desc *d, const fcn_pn_params *p, cons
     const int B = d->B, L = d->L, K = d->K, C1 = d->C1, C2 = d->C2, C3 = d->C3;
     const int cap = L * K;
     const double M = (double)B * (double)L * (double)K;
-    const int tr = d->training ? 1 : 0;
-    // a key-pooled training forward hands the winners' pre-BN values to its backward through ws->gmax (fcn_hip.h)
-    if (tr && ws->amax && !ws->gmax && fcn_pn_key_pool(d, ws, C3)) return FCN_E_BADARG;
+    const int tr = uses_batch_stats(d) ? 1 : 0;         // batch sums + running-stat update
+    const int sv = saves_for_backward(d) ? 1 : 0;       // y2, y3, amax, gmax (key pool) and the zeroed bstat for a backward
+    // a key-pooled training / frozen forward hands the winners' pre-BN values to its backward through ws->gmax (fcn_hip.h)
+    if (sv && ws->amax && !ws->gmax && fcn_pn_key_pool(d, ws, C3)) return FCN_E_BADARG;
     float *bn1 = ws->bn + fcn_bn_off(0, C1, C2);
     float *bn2 = ws->bn + fcn_bn_off(1, C1, C2);
     float *bn3 = ws->bn + fcn_bn_off(2, C1, C2);
@@ -923,7 +925,7 @@ extern "C" int fcn_pn_forward(const fcn_pn_desc *d, const fcn_pn_params *p, cons
     a.ent = (const float4 *)ws->ent; a.woff = ws->woff; a.tiles = ws->tiles; a.L = L; a.cap = cap; a.tps = (cap + 127) / 128;
     a.aprev = nullptr; a.bn_in = bn1; a.W1 = p->W[0]; a.Wenc = (const u32x4 *)(ws->wenc + pn_wenc_off(0, C1, C2, C3)); a.y = ws->y2;
     a.flags = ws->flags;
-    a.stat = tr ? st2 : nullptr; a.CIN = C1; a.COUT = C2;
+    a.stat = tr ? st2 : nullptr; a.save_y = sv; a.CIN = C1; a.COUT = C2;
     a.stat_in = nullptr; a.gamma_in = a.beta_in = nullptr; a.rmean_in = a.rvar_in = nullptr; a.nbt_in = nullptr; a.bn_pub = nullptr;
     a.M = M; a.eps = d->eps; a.momentum = d->momentum; a.rep_stride = 2 * C2 + 2 * C3;
     a.ewin = nullptr; a.pkey = nullptr; a.gamma_out = nullptr;
@@ -931,7 +933,7 @@ extern "C" int fcn_pn_forward(const fcn_pn_desc *d, const fcn_pn_params *p, cons
 
     // BN2 is finalised by conv3's workgroups (no launch in between)
     a.aprev = ws->y2; a.bn_in = bn2; a.W1 = nullptr; a.Wenc = (const u32x4 *)(ws->wenc + pn_wenc_off(1, C1, C2, C3)); a.y = ws->y3;
-    a.stat = tr ? st3 : nullptr; a.CIN = C2; a.COUT = C3;
+    a.stat = tr ? st3 : nullptr; a.save_y = sv; a.CIN = C2; a.COUT = C3;
     a.stat_in = tr ? st2 : nullptr; a.gamma_in = p->gamma[1]; a.beta_in = p->beta[1];
     a.rmean_in = p->running_mean[1]; a.rvar_in = p->running_var[1]; a.nbt_in = p->num_batches_tracked[1]; a.bn_pub = bn2;
     // position-major features + a key buffer in the workspace: the max-pool rides in conv3's epilogue (pool_keys_kernel finishes it)
@@ -958,15 +960,15 @@ extern "C" int fcn_pn_forward(const fcn_pn_desc *d, const fcn_pn_params *p, cons
         int wpb = nsub;
         while ((int64_t)B * ((L + wpb - 1) / wpb) > 1024 && wpb < 8 * nsub) wpb += nsub;       // ~ two workgroups per CU at least
         hipLaunchKernelGGL(pool_keys_kernel, dim3((L + wpb - 1) / wpb, B), dim3(GT), 0, st, (unsigned long long *)ws->pkey, pb, cnt,
-                           feat, tr ? ws->amax : nullptr, tr ? ws->gmax : nullptr, L, C3, wpb, tr ? ws->bstat : nullptr, nz,
+                           feat, sv ? ws->amax : nullptr, sv ? ws->gmax : nullptr, L, C3, wpb, sv ? ws->bstat : nullptr, nz,
                            (const void *)ws->y3, cap, s16 ? 1 : 0);
     } else if (nlc_pool) {
         PoolBn pb;
         pb.stat = tr ? st3 : nullptr; pb.rep_stride = 2 * C2 + 2 * C3; pb.gamma = p->gamma[2]; pb.beta = p->beta[2];
         pb.rmean = p->running_mean[2]; pb.rvar = p->running_var[2]; pb.nbt = p->num_batches_tracked[2]; pb.bn = bn3;
         pb.M = M; pb.eps = d->eps; pb.momentum = d->momentum;
-        int32_t *am = tr ? ws->amax : nullptr;
-        double *zp = tr ? ws->bstat : nullptr;
+        int32_t *am = sv ? ws->amax : nullptr;
+        double *zp = sv ? ws->bstat : nullptr;
         // waves per window by the window capacity (nsample): 4 from 128 rows up, else 1 (measured: two waves per window at
         // nsample 64 are SLOWER than one -- 83 -> 96 us for the scale -- the exchange costs more than the shorter walk saves)
 #define FCN_POOL_LAUNCH2(VEC_, S16_)                                                                                  \
@@ -981,9 +983,9 @@ extern "C" int fcn_pn_forward(const fcn_pn_desc *d, const fcn_pn_params *p, cons
     } else {
         dim3 pgrid((L + PW - 1) / PW, C3 / 64, B);
         if (s16) hipLaunchKernelGGL(pool_kernel<1>, pgrid, dim3(GT), 0, st, ws->y3, bn3, ws->woff, cnt, one_hot, feat,
-                                    tr ? ws->amax : nullptr, L, cap, C3, d->nvec, d->nlc, tr ? ws->bstat : nullptr, nz);
+                                    sv ? ws->amax : nullptr, L, cap, C3, d->nvec, d->nlc, sv ? ws->bstat : nullptr, nz);
         else hipLaunchKernelGGL(pool_kernel<0>, pgrid, dim3(GT), 0, st, ws->y3, bn3, ws->woff, cnt, one_hot, feat,
-                                tr ? ws->amax : nullptr, L, cap, C3, d->nvec, d->nlc, tr ? ws->bstat : nullptr, nz);
+                                sv ? ws->amax : nullptr, L, cap, C3, d->nvec, d->nlc, sv ? ws->bstat : nullptr, nz);
     }
     FCN_CHECK_LAUNCH();
     return 0;
@@ -1007,7 +1009,7 @@ extern "C" int fcn_pn_conv_fwd(const fcn_pn_desc *d, const fcn_pn_params *p, con
     a.M = 1.0; a.eps = d->eps; a.momentum = d->momentum;       // the BN in front is read finished from ws->bn
     a.rep_stride = 2 * C2 + 2 * C3;
     a.flags = ws->flags;
-    a.ewin = nullptr; a.pkey = nullptr; a.gamma_out = nullptr;
+    a.ewin = nullptr; a.pkey = nullptr; a.gamma_out = nullptr; a.save_y = 1;
     if (layer == 2) {
         a.aprev = nullptr; a.bn_in = ws->bn + fcn_bn_off(0, C1, C2); a.W1 = p->W[0]; a.Wenc = (const u32x4 *)(ws->wenc + pn_wenc_off(0, C1, C2, C3)); a.y = ws->y2;
         a.stat = with_stats ? st2 : nullptr; a.CIN = C1; a.COUT = C2;

@@ -33,6 +33,14 @@ from . import box_ops
 from . import _native
 
 
+def _bn_mode(module):
+    """BatchNorm mode (_native.BN_*) of a PointNet scale or a ConvFeatNet: frozen (freeze_bn) in train() and eval() alike,
+    else batch statistics in train() and running statistics in eval()."""
+    if getattr(module, "bn_frozen", False):
+        return _native.BN_FROZEN
+    return _native.BN_TRAIN if module.training else _native.BN_RUNNING
+
+
 class PointNetModule(nn.Module):
     """Single-scale PointNet (reference: models/det_base.py:35-103)."""
 
@@ -53,6 +61,14 @@ class PointNetModule(nn.Module):
         init_params([self.conv1[0], self.conv2[0], self.conv3[0]], 'kaiming_normal')
         init_params([self.conv1[1], self.conv2[1], self.conv3[1]], 1)
         self._pool = WorkspacePool()
+        self.bn_frozen = False
+
+    def freeze_bn(self, flag=True):
+        """Frozen BatchNorm (module state like .training, not in the state_dict): in train() and eval() alike the three BatchNorms
+        normalise with their running statistics, never change them, and the forward carries a graph whenever gradients are enabled
+        and a parameter requires them -- the reference's model.eval() fine-tune.  Returns self."""
+        self.bn_frozen = bool(flag)
+        return self
 
     def _param_pack(self):
         convs = (self.conv1, self.conv2, self.conv3)
@@ -69,7 +85,7 @@ class PointNetModule(nn.Module):
         nlc=True: position-major (B, L, C3) without the one-hot rows (what the fused ConvFeatNet consumes)."""
         params, bufs = self._param_pack()
         bn = self.conv1[1]
-        feat, _, _ = pointnet_pooled(self._pool, self.dist, self.nsample, self.training, bn.eps,
+        feat, _, _ = pointnet_pooled(self._pool, self.dist, self.nsample, _bn_mode(self), bn.eps,
                                      bn_momentum(bn),
                                      pc.contiguous(), new_pc.contiguous(), one_hot_vec, bufs, params, nlc=nlc)
         return feat
@@ -78,7 +94,7 @@ class PointNetModule(nn.Module):
         """Enqueue this scale's forward kernels now, create the autograd node later with attach_pooled()."""
         params, bufs = self._param_pack()
         bn = self.conv1[1]
-        return launch_pooled(self._pool, self.dist, self.nsample, self.training, bn.eps,
+        return launch_pooled(self._pool, self.dist, self.nsample, _bn_mode(self), bn.eps,
                              bn_momentum(bn),
                              pc.contiguous(), new_pc.contiguous(), one_hot_vec, bufs, params, nlc=nlc)
 
@@ -87,7 +103,7 @@ class PointNetModule(nn.Module):
         from .pointnet_fused import prepare_pooled
         params, bufs = self._param_pack()
         bn = self.conv1[1]
-        return prepare_pooled(self._pool, self.dist, self.nsample, self.training, bn.eps, bn_momentum(bn),
+        return prepare_pooled(self._pool, self.dist, self.nsample, _bn_mode(self), bn.eps, bn_momentum(bn),
                               pc.contiguous(), new_pc.contiguous(), one_hot_vec, bufs, params, nlc=nlc)
 
     def attach_pooled(self, handle):
@@ -95,21 +111,21 @@ class PointNetModule(nn.Module):
         return feat
 
     def front_signature(self, nlc=False):
-        """Everything a prepared handle (prepare_pooled) FREEZES besides the input tensors: the configuration tuple (training,
+        """Everything a prepared handle (prepare_pooled) FREEZES besides the input tensors: the configuration tuple (BatchNorm mode,
         need_grad, BatchNorm eps / momentum, layout), the operand precision and where the parameters and BatchNorm buffers live.
         A prefetched front is only consumed by a forward that would have prepared the same handle."""
         from .pointnet_fused import _cfg_tuple
         from . import precision as _precision
         params, bufs = self._param_pack()
         bn = self.conv1[1]
-        cfgt = _cfg_tuple(self.dist, self.nsample, self.training, bn.eps, bn_momentum(bn), params, nlc)
+        cfgt = _cfg_tuple(self.dist, self.nsample, _bn_mode(self), bn.eps, bn_momentum(bn), params, nlc)
         return (cfgt, _precision.code(), tuple(t.data_ptr() for t in params), tuple(t.data_ptr() for b in bufs for t in b))
 
     def forward(self, pc, feat, new_pc=None):
         """Reference-shaped output (B, C3, L, nsample), masked (models/det_base.py:62-103), expanded from the fused path's per-entry
-        activations with device-side indexing.  With gradients enabled (training mode, a parameter that requires them) the
-        return carries its graph, as the reference's does: the backward sums the slots back onto the entry rows and runs the
-        HIP backward chain (pointnet_fused.dense_pointnet).  Training inside PointNetDet goes through forward_pooled, which never
+        activations with device-side indexing.  With gradients enabled (training mode or freeze_bn(), a parameter that requires
+        them) the return carries its graph, as the reference's does: the backward sums the slots back onto the entry rows and runs
+        the HIP backward chain (pointnet_fused.dense_pointnet).  Training inside PointNetDet goes through forward_pooled, which never
         materialises the K slots."""
         from .pointnet_fused import dense_from_entries, dense_pointnet
         params, bufs = self._param_pack()
@@ -117,18 +133,19 @@ class PointNetModule(nn.Module):
         if pc.requires_grad and torch.is_grad_enabled():
             raise RuntimeError("PointNetModule.forward: no gradient w.r.t. the point cloud (the reference never asks for one either: "
                                "its inputs do not require grad)")
+        mode = _bn_mode(self)
         if torch.is_grad_enabled() and any(p.requires_grad for p in params):
-            if not self.training:
+            if mode == _native.BN_RUNNING:
                 # (the reference returns a differentiable tensor here too -- fine-tuning under frozen BatchNorm; the HIP backward
                 # chain differentiates batch-statistics BatchNorm only, so this raises instead of handing back a tensor without a graph)
                 raise NotImplementedError(
                     "PointNetModule.forward in eval mode with gradients enabled and trainable parameters: the backward of "
-                    "running-statistics BatchNorm is not implemented; wrap the call in torch.no_grad() (inference) or call "
-                    ".train() (training)")
-            return dense_pointnet(self._pool, self.dist, self.nsample, True, bn.eps, bn_momentum(bn),
+                    "running-statistics BatchNorm is not implemented; wrap the call in torch.no_grad() (inference), call "
+                    ".train() (training) or .freeze_bn() (fine-tuning through the running statistics)")
+            return dense_pointnet(self._pool, self.dist, self.nsample, mode, bn.eps, bn_momentum(bn),
                                   pc.contiguous(), new_pc.contiguous(), bufs, params)
         with torch.no_grad():
-            return dense_from_entries(self._pool, self.dist, self.nsample, self.training, bn.eps,
+            return dense_from_entries(self._pool, self.dist, self.nsample, mode, bn.eps,
                                       bn_momentum(bn),
                                       pc.contiguous(), new_pc.contiguous(), bufs, params)
 
@@ -199,11 +216,29 @@ class PointNetFeat(nn.Module):
     def nets(self):
         return tuple(getattr(self, "pointnet%d" % (i + 1)) for i in range(self.num_scales))
 
+    def freeze_bn(self, flag=True):
+        """PointNetModule.freeze_bn on every scale.  Returns self."""
+        for net in self.nets:
+            net.freeze_bn(flag)
+        return self
+
+    @property
+    def bn_frozen(self):
+        return self.bn_mode() == _native.BN_FROZEN
+
+    def bn_mode(self):
+        """The BatchNorm mode of the scales (_native.BN_*), which must agree: the fused front takes one mode for all of them."""
+        flags = set(bool(getattr(net, "bn_frozen", False)) for net in self.nets)
+        if len(flags) > 1:
+            raise ValueError("PointNetFeat: the scales disagree on freeze_bn (%s); freeze all of them or none"
+                             % [bool(net.bn_frozen) for net in self.nets])
+        return _bn_mode(self.nets[0])
+
     def _front_key(self, point_cloud, sample_pc, one_hot_vec, nlc, training):
         # the inputs as prefetch() saw them (storage, shape, version counter; a non-contiguous tensor is keyed as passed) and
         # what the prepared handles froze: configuration, precision, parameter / buffer storage of every scale
         ts = [point_cloud] + list(sample_pc) + ([] if one_hot_vec is None else [one_hot_vec])
-        return (tuple((t.data_ptr(), tuple(t.shape), tuple(t.stride()), t._version) for t in ts), bool(nlc), bool(training),
+        return (tuple((t.data_ptr(), tuple(t.shape), tuple(t.stride()), t._version) for t in ts), bool(nlc), int(training),
                 torch.is_grad_enabled(), tuple(net.front_signature(nlc) for net in self.nets))
 
     def prefetch(self, point_cloud, sample_pc, one_hot_vec=None, nlc=False, before=None):
@@ -238,7 +273,7 @@ class PointNetFeat(nn.Module):
         for t in [point_cloud] + list(sample_pc):
             t.record_stream(side)
         # cap: the hipGraph capture these launches belong to (0: none -- they really ran)
-        self._prefetched = {"key": self._front_key(point_cloud, sample_pc, one_hot_vec, nlc, self.training), "handles": prepared,
+        self._prefetched = {"key": self._front_key(point_cloud, sample_pc, one_hot_vec, nlc, self.bn_mode()), "handles": prepared,
                             "event": ev_out, "dev": dev, "cap": _native.capture_id(dev)}
         return True
 
@@ -284,6 +319,7 @@ class PointNetFeat(nn.Module):
         nets = self.nets
         ns = self.num_scales
         self.done_events = None
+        mode = self.bn_mode()
         if not (self.concurrent_scales and point_cloud.is_cuda) or os.environ.get("FCN_SERIAL", "0") == "1":
             self.drop_prefetch()
             for net in nets:
@@ -306,7 +342,7 @@ class PointNetFeat(nn.Module):
         prepared = None
         if self._prefetched is not None and (self._prefetch_is_foreign() or
                                              self._prefetched["key"] != self._front_key(point_cloud, sample_pc, one_hot_vec, nlc,
-                                                                                        self.training)):
+                                                                                        mode)):
             self.drop_prefetch()
         if self.fused_front:
             from .pointnet_fused import group_compact, launch_prepared
@@ -323,7 +359,7 @@ class PointNetFeat(nn.Module):
         sts = [streams[i] for i in range(ns - 1)] + [cur]
         self._step_id += 1
         for k in range(ns):                  # where each scale's backward will be enqueued (read by its autograd node)
-            host = self.bwd_share.get(k) if (self.share_active and self.training) else None
+            host = self.bwd_share.get(k) if (self.share_active and mode != _native.BN_RUNNING) else None
             pool = nets[k]._pool
             pool.fwd_step = self._step_id
             pool.bwd_stream = None if host is None else streams[host]
@@ -400,6 +436,23 @@ class ConvFeatNet(nn.Module):
             if isinstance(m, nn.BatchNorm1d):
                 m.weight.data.fill_(1)
                 m.bias.data.zero_()
+        self.bn_frozen = False
+
+    def freeze_bn(self, flag=True):
+        """Frozen BatchNorm (module state like .training, not in the state_dict): in train() and eval() alike every BatchNorm of the
+        FCN normalises with its running statistics and never changes them; the fused forward carries a graph whenever gradients
+        are enabled and a parameter or an input map requires them.  The nn.BatchNorm1d modules of the module path
+        (PointNetDet.fused_fcn = False) are held in eval mode meanwhile.  Returns self."""
+        self.bn_frozen = bool(flag)
+        return self.train(self.training)
+
+    def train(self, mode=True):
+        super(ConvFeatNet, self).train(mode)
+        if getattr(self, "bn_frozen", False):
+            for m in self.modules():
+                if isinstance(m, nn.BatchNorm1d):
+                    m.train(False)
+        return self
 
     def forward(self, *xs):
         assert len(xs) == self.LEVELS
@@ -506,6 +559,19 @@ class PointNetDet(nn.Module):
         self.last_logits = None
         self.last_logits64 = None
         self.last_num_fg = None
+
+    def freeze_bn(self, flag=True):
+        """Frozen BatchNorm everywhere (PointNet scales and ConvFeatNet): the reference's model.eval() fine-tune, in train() and
+        eval() alike -- running statistics, never updated, gradients through them.  model.feat_net.freeze_bn() /
+        model.conv_net.freeze_bn() freeze one part only.  Returns self."""
+        self.feat_net.freeze_bn(flag)
+        self.conv_net.freeze_bn(flag)
+        return self
+
+    def _differentiates(self):
+        """Whether this forward builds a graph a backward will run through: gradients enabled and training mode or frozen BatchNorm
+        in some part (the step-loop machinery -- split backward, next-batch prefetch -- follows it)."""
+        return torch.is_grad_enabled() and (self.training or self.feat_net.bn_frozen or getattr(self.conv_net, "bn_frozen", False))
 
     def detect(self, data_dicts, unit_group=None, num_groups=None, method=None, thresh=None, top_k=300):
         """Inference tail on the device (train/test_net_det.py:193-293 + :126-152): eval forward, decode into label-format
@@ -686,14 +752,14 @@ class PointNetDet(nn.Module):
                                   [r.shape[2] for r in refs], one_hot_vec, dev)
             self.feat_net.share_active = True          # (every scale's gradient comes out of ONE fcn_convnet_backward call)
             feats = self.feat_net(xyz, refs, None, one_hot_vec, nlc=True, join=False)
-            if self.split_backward and self.training and torch.is_grad_enabled():
+            if self.split_backward and self._differentiates():
                 # two-phase backward (backward_split): the FCN sees detached leaves, so loss.backward() stops at the pooled
                 # feature maps and the PointNet scales are differentiated by a second call
                 leaves = tuple(f.detach().requires_grad_(True) for f in feats)
                 self._split = (feats, leaves)
                 feats = leaves
             nxt = getattr(self, "next_batch", None)
-            if nxt is not None and self.training and torch.is_grad_enabled():
+            if nxt is not None and self._differentiates():
                 # the caller announced the NEXT batch (model.next_batch = data_dicts): start its batch-only front here, on a side
                 # branch beside the latency-bound ConvFeatNet forward whose launches leave most CUs idle (instead of a
                 # model.prefetch() call between forward and backward, which lands beside the first backward launches)
@@ -754,7 +820,7 @@ class PointNetDet(nn.Module):
                     logits64, batch_size, num_out, cls_label, refs[1], center_label, heading_label, size_label,
                     size_class_label, mean_size_array, self.num_bins, self.num_size_cluster, wts,
                     self._loss_scratch[1])
-                if not (self.defer_metrics_join and self.training and torch.is_grad_enabled()):
+                if not (self.defer_metrics_join and self._differentiates()):
                     self._iou_metrics.join()
                 iou2, iou3, iout = ious[0], ious[1], ious[2]
             else:

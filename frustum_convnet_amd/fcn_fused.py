@@ -110,7 +110,7 @@ def _prepare(pool, cfgt, bufs, one_hot, B, Ls, dev, pt):
         bh = torch.cat([cls_b, reg_b], 0).contiguous()
     nvec = 0 if one_hot is None else one_hot.shape[1]
     oh = None if one_hot is None else one_hot.detach().contiguous().float()
-    desc = CnDesc(B, (ctypes.c_int32 * CN_MAXLEV)(*Ls), nvec, reg_w.shape[0], 1 if training else 0, eps, momentum, 0,
+    desc = CnDesc(B, (ctypes.c_int32 * CN_MAXLEV)(*Ls), nvec, reg_w.shape[0], int(training), eps, momentum, 0,
                   _precision.code(), nlev, Ws[0].shape[0])
     ws = pool.acquire((B,) + tuple(Ls) + (nvec, reg_w.shape[0]), desc, dev, need_grad)
     rmeans, rvars, nbts = bufs
@@ -240,13 +240,27 @@ def _gather(conv_net, cls_out, reg_out):
     return pt, bufs, bn0
 
 
+def bn_mode(conv_net):
+    """The BatchNorm mode (_native.BN_*) of a ConvFeatNet: frozen (freeze_bn) in train() and eval() alike, else by .training."""
+    if getattr(conv_net, "bn_frozen", False):
+        return _native.BN_FROZEN
+    return _native.BN_TRAIN if conv_net.training else _native.BN_RUNNING
+
+
+def _cn_cfg(conv_net, bn0, wants_grad):
+    """(mode, eps, momentum, need_grad) of one forward: a frozen forward nothing will differentiate takes the inference path."""
+    mode = bn_mode(conv_net)
+    need_grad = mode != _native.BN_RUNNING and torch.is_grad_enabled() and bool(wants_grad)
+    if mode == _native.BN_FROZEN and not need_grad:
+        mode = _native.BN_RUNNING
+    return (mode, float(bn0.eps), bn_momentum(bn0), need_grad)
+
+
 def convnet_prepack(pool, conv_net, cls_out, reg_out, B, Ls, one_hot, device):
     """Starts the weight re-packing of the coming convnet_fused() call on the pool's side stream (forked from the current
     stream) and returns the handle to pass as `pre`: 25 us that overlap the PointNet scales instead of heading the FCN."""
     pt, bufs, bn0 = _gather(conv_net, cls_out, reg_out)
-    training = conv_net.training
-    need_grad = bool(training) and torch.is_grad_enabled() and any(t.requires_grad for t in pt)
-    cfgt = (bool(training), float(bn0.eps), bn_momentum(bn0), need_grad)
+    cfgt = _cn_cfg(conv_net, bn0, any(t.requires_grad for t in pt))
     cur = torch.cuda.current_stream(device)
     side, ev = pool.pack_stream(device)
     side.wait_stream(cur)
@@ -276,10 +290,7 @@ def convnet_fused(pool, conv_net, cls_out, reg_out, feats, one_hot, pre=None, fe
     if not feats[0].is_cuda:
         raise RuntimeError("frustum_convnet_amd: fused ConvFeatNet runs on the GPU only")
     pt, bufs, bn0 = _gather(conv_net, cls_out, reg_out)
-    training = conv_net.training
-    need_grad = bool(training) and torch.is_grad_enabled() and (
-        any(t.requires_grad for t in pt) or any(f.requires_grad for f in feats))
-    cfgt = (bool(training), float(bn0.eps), bn_momentum(bn0), need_grad)
+    cfgt = _cn_cfg(conv_net, bn0, any(t.requires_grad for t in pt) or any(f.requires_grad for f in feats))
     if pre is not None and pre["cfgt"] != cfgt:        # e.g. only the features require grad: pack inline instead
         pool.release(pre["ws"])
         torch.cuda.current_stream(feats[0].device).wait_event(pre["event"])

@@ -159,7 +159,7 @@ def _acquire(pool, cfgt, pc, ref, one_hot, bufs, plist, need_grad):
     nvec = 0 if (one_hot is None or nlc) else one_hot.shape[1]
     dev = pc.device
     ws = pool.acquire(B, N, Lw, K, C1, C2, C3, device=dev, need_grad=need_grad)
-    desc = PnDesc(B, N, Lw, K, C1, C2, C3, nvec, 1 if training else 0, eps, momentum, 1 if nlc else 0,
+    desc = PnDesc(B, N, Lw, K, C1, C2, C3, nvec, int(training), eps, momentum, 1 if nlc else 0,
                   _precision.code(), 0)
     rmeans, rvars, nbts = bufs
     Wc = [W1.detach().reshape(C1, 3).contiguous(), W2.detach().reshape(C2, C1).contiguous(),
@@ -335,9 +335,16 @@ class _PointNetPooled(torch.autograd.Function):
         return (None, None, None, None, None, None, None, None) + tuple(outs)
 
 
-def _cfg_tuple(dist, nsample, training, eps, momentum, params, nlc):
-    need_grad = bool(training) and torch.is_grad_enabled() and any(t.requires_grad for t in params)
-    return (float(dist), int(nsample), bool(training), float(eps), float(momentum), need_grad, bool(nlc))
+def _cfg_tuple(dist, nsample, mode, eps, momentum, params, nlc):
+    """mode: the BatchNorm mode (_native.BN_*; a bool is read as train / running).  A frozen forward that nothing will differentiate
+    takes the inference path (BN_RUNNING: the same statistics, nothing saved)."""
+    mode = int(mode)
+    if mode not in (_native.BN_RUNNING, _native.BN_TRAIN, _native.BN_FROZEN):
+        raise ValueError("unknown BatchNorm mode %r" % (mode,))
+    need_grad = mode != _native.BN_RUNNING and torch.is_grad_enabled() and any(t.requires_grad for t in params)
+    if mode == _native.BN_FROZEN and not need_grad:
+        mode = _native.BN_RUNNING
+    return (float(dist), int(nsample), mode, float(eps), float(momentum), need_grad, bool(nlc))
 
 
 def _check_device(pc):
@@ -410,7 +417,8 @@ def dense_from_entries(pool, dist, nsample, training, eps, momentum, pc, ref, bu
     autograd graph (dense_pointnet() is the differentiable form)."""
     if not pc.is_cuda:
         raise RuntimeError("frustum_convnet_amd: MI355X only; no CPU fallback")
-    cfgt = (float(dist), int(nsample), bool(training), float(eps), float(momentum))
+    mode = _native.BN_RUNNING if int(training) == _native.BN_FROZEN else int(training)     # (nothing saved: the inference path)
+    cfgt = (float(dist), int(nsample), mode, float(eps), float(momentum))
     feat, idx, cnt, ws, desc, _ = _forward_impl(pool, cfgt, pc, ref, None, bufs, params, False)
     B, L, K, C3 = desc.B, desc.L, desc.K, desc.C3
     rows, a3, live = _dense_view(ws, desc, cnt, pc.device)

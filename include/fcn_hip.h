@@ -95,11 +95,26 @@ int fcn_query_depth_point_multi_f32(int nscale, const float *pts_z, int64_t pt_s
  * (window, point) pair is evaluated once and carries its multiplicity as a weight.
  * Channel widths C1,C2,C3 must be multiples of 64; L <= 8192; K <= 1024.
  * ------------------------------------------------------------------------------------------- */
+/* BatchNorm modes (fcn_pn_desc.training, fcn_cn_desc.training):
+ *   FCN_BN_TRAIN    batch statistics; the running statistics (running_mean, running_var, num_batches_tracked) are updated;
+ *                   the forward saves what the backward reads.
+ *   FCN_BN_RUNNING  running statistics, nothing saved: inference.  Every backward entry returns FCN_E_BADARG.
+ *   FCN_BN_FROZEN   running statistics, which are never written, and the forward saves what the backward reads (the
+ *                   reference's model.eval() fine-tune, torchvision's FrozenBatchNorm).  The backward differentiates through the
+ *                   running statistics: dy = gamma * rstd_running * dz (no batch-mean terms), dgamma = sum dz * xhat,
+ *                   dbeta = sum dz.  fcn_pn_group_compact[2] folds BN1 from the running statistics, fcn_pn_forward /
+ *                   fcn_convnet_pack / fcn_convnet_forward[2] take the training forward's launches without the batch sums,
+ *                   every fcn_pn_backward* / fcn_convnet_backward accepts it, in all four FCN_PREC_* modes.
+ * Any other value: FCN_E_BADARG from every entry point that reads the descriptor's mode. */
+#define FCN_BN_RUNNING 0
+#define FCN_BN_TRAIN   1
+#define FCN_BN_FROZEN  2
+
 typedef struct fcn_pn_desc {
     int32_t B, N, L, K;          /* frustums, points per frustum, windows, nsample        */
     int32_t C1, C2, C3;          /* MLP widths                                              */
     int32_t nvec;                /* one-hot width appended after pooling (0..)              */
-    int32_t training;            /* 1: batch statistics (+ running-stat update), 0: running */
+    int32_t training;            /* BatchNorm mode, FCN_BN_* (below)                        */
     float   eps, momentum;       /* BatchNorm eps (1e-5) and momentum (0.1)                 */
     int32_t nlc;                 /* 0: feat/dfeat are (B, C3+nvec, L) as the reference returns them;
                                     1: position-major (B, L, C3), no one-hot rows (input of fcn_convnet_*) */
@@ -131,14 +146,14 @@ typedef struct fcn_pn_ws {
     double  *stat;               /* 16 + fcn_stat_replicas() * (2*C2 + 2*C3) doubles: input moments, then the
                                     replicated sum / sumsq blocks of conv2 and conv3                        */
     float   *bn;                 /* 4*(C1+C2+C3) floats: per layer scale, shift, mean, rstd  */
-    /* backward -- and, for gmax, the hand-over from a key-pooled TRAINING forward to its backward */
+    /* backward -- and, for gmax, the hand-over from a key-pooled TRAINING or FROZEN forward to its backward */
     float   *gmax;               /* (B, L, C3)  dfeat routed to the max rows (written by fcn_pn_backward*).  When the forward
-                                    pooled through keys (training = 1, nlc = 1, pkey and ewin set) fcn_pn_forward ALSO writes
+                                    pooled through keys (training = FCN_BN_TRAIN or FCN_BN_FROZEN, nlc = 1, pkey and ewin set) fcn_pn_forward ALSO writes
                                     it: the winners' pre-BN values, position-major, which the first backward kernel reads and
                                     then overwrites with the routed gradient.  Between such a forward and its backward the
                                     buffer is therefore LIVE: do not clear it, do not share it between scales or workspace
-                                    sets in flight, and pass the same pointer to both calls.  A training key-pool forward
-                                    with amax set and gmax NULL returns FCN_E_BADARG                                         */
+                                    sets in flight, and pass the same pointer to both calls.  A training / frozen key-pool
+                                    forward with amax set and gmax NULL returns FCN_E_BADARG                                         */
     float   *dy3;                /* (B, cap, C3), or NULL: dy3 is not materialised -- conv3's weight-gradient GEMM rebuilds
                                     it from y3, ewin, amax, gmax and the BN3-backward sums while staging (bit-identical dW3;
                                     measured 0.7 % slower over the step, saves B*cap*C3 floats) */
@@ -212,14 +227,14 @@ int fcn_pn_pack_weights(const fcn_pn_desc *d, const fcn_pn_params *p, const fcn_
 int fcn_pn_pack_weights_all(int nscale, const fcn_pn_desc *const *d, const fcn_pn_params *const *p,
                             const fcn_pn_ws *const *ws, void *stream);
 
-/* Whole forward of one scale after fcn_pn_compact: feat (B, C3+nvec, L), one_hot (B,nvec) or NULL.  In training mode its
+/* Whole forward of one scale after fcn_pn_compact: feat (B, C3+nvec, L), one_hot (B,nvec) or NULL.  In training and frozen mode its
  * last kernel also zeroes ws.bstat (when non-NULL) for the fcn_pn_backward that follows -- and, when the max-pool is taken
  * from keys (nlc = 1, ws.pkey and ws.ewin set), writes the winners' pre-BN values into ws.gmax, which the following
  * fcn_pn_backward* reads before overwriting it (see fcn_pn_ws.gmax; FCN_E_BADARG when ws.amax is set and ws.gmax is NULL). */
 int fcn_pn_forward(const fcn_pn_desc *d, const fcn_pn_params *p, const int32_t *cnt,
                    const float *one_hot, const fcn_pn_ws *ws, float *feat, void *stream);
 
-/* Backward: dfeat (B, C3+nvec, L) -> dW[3], dgamma[3], dbeta[3] (overwritten, not accumulated).  After a key-pooled training
+/* Backward: dfeat (B, C3+nvec, L) -> dW[3], dgamma[3], dbeta[3] (overwritten, not accumulated).  After a key-pooled training / frozen
  * forward (fcn_pn_forward above) it expects ws.gmax exactly as that forward left it.  dW[1] and dW[2] must be
  * 16-byte aligned (FCN_E_BADARG otherwise): the fixed-order sum of the split partials writes 16-byte vectors.  Size limits
  * (FCN_E_LIMIT): B * cap * max(C2, C3) < 2^31 elements (32-bit offsets) and B * cap < 2^24 entry rows (24-bit row multiplies). */
@@ -269,7 +284,7 @@ typedef struct fcn_cn_desc {
     int32_t L[FCN_CN_MAXLEV];    /* positions of the pooled feature maps (L[1] is the output length); L[j+1] = conv(L[j], k3 s2 p1) */
     int32_t nvec;                /* one-hot width                                                               */
     int32_t reg_out;             /* regression head width (39 for KITTI, 67 for SUN-RGBD); 2 + reg_out <= 128   */
-    int32_t training;
+    int32_t training;            /* BatchNorm mode, FCN_BN_* (see fcn_pn_desc)                                  */
     float   eps, momentum;
     int32_t prepacked;           /* 1: fcn_convnet_pack already ran for these weights / one-hot (joined by the caller) */
     int32_t precision;           /* FCN_PREC_*                                                                  */
