@@ -31,12 +31,26 @@ FCN_HD float fcn_poly_area2(const float *x, const float *z, int n)
     return s;
 }
 
-// Area of the intersection of two convex quadrilaterals given as cyclic vertex lists (either orientation).
-FCN_HD float fcn_quad_intersection_area(const float *ax, const float *az, const float *bx, const float *bz)
+// Twice the signed area of a quadrilateral, taken on coordinates RELATIVE to its vertex 0 (the terms that contain vertex 0
+// vanish).  Areas are translation-invariant, the float32 shoelace is not: on absolute coordinates it subtracts products of
+// x * z (thousands of m^2 at a depth of 80 m) to get a few m^2, a relative error of 1e-4 and more at the far end of the KITTI
+// range.  The differences to a vertex of the same box are exact or nearly so.
+FCN_HD float fcn_quad_area2(const float *x, const float *z)
 {
-    float px[FCN_CLIP_MAXV], pz[FCN_CLIP_MAXV], qx[FCN_CLIP_MAXV], qz[FCN_CLIP_MAXV];
+    const float x1 = x[1] - x[0], x2 = x[2] - x[0], x3 = x[3] - x[0];
+    const float z1 = z[1] - z[0], z2 = z[2] - z[0], z3 = z[3] - z[0];
+    return (x1 * z2 - x2 * z1) + (x2 * z3 - x3 * z2);
+}
+
+// Area of the intersection of two convex quadrilaterals given as cyclic vertex lists (either orientation).  Both are moved
+// by -(ax[0], az[0]) first: the clip and the final shoelace then work on coordinates of the size of the boxes, whatever
+// the depth (see fcn_quad_area2).
+FCN_HD float fcn_quad_intersection_area(const float *ax, const float *az, const float *bx_, const float *bz_)
+{
+    float px[FCN_CLIP_MAXV], pz[FCN_CLIP_MAXV], qx[FCN_CLIP_MAXV], qz[FCN_CLIP_MAXV], bx[4], bz[4];
     int n = 4;
-    for (int i = 0; i < 4; ++i) { px[i] = ax[i]; pz[i] = az[i]; }
+    const float ox = ax[0], oz = az[0];
+    for (int i = 0; i < 4; ++i) { px[i] = ax[i] - ox; pz[i] = az[i] - oz; bx[i] = bx_[i] - ox; bz[i] = bz_[i] - oz; }
     const float sgn = fcn_poly_area2(bx, bz, 4) >= 0.f ? 1.f : -1.f;      // interior side of b's edges
     for (int e = 0; e < 4; ++e) {
         const float c1x = bx[e], c1z = bz[e];
@@ -89,7 +103,7 @@ FCN_HD void fcn_iou_from_polys(const float *ax, const float *az, float a_ytop, f
     *iou3d = 0.f;
     const float inter = fcn_quad_intersection_area(ax, az, bx, bz);
     if (!(inter > 0.f)) return;                                          // empty intersection: the reference leaves zeros
-    float aa = 0.5f * fcn_poly_area2(ax, az, 4), ab = 0.5f * fcn_poly_area2(bx, bz, 4);
+    float aa = 0.5f * fcn_quad_area2(ax, az), ab = 0.5f * fcn_quad_area2(bx, bz);
     aa = aa < 0.f ? -aa : aa;
     ab = ab < 0.f ? -ab : ab;
     const float uni = aa + ab - inter;

@@ -91,7 +91,10 @@ def cube_nms(dets, thresh, top_k=300):
     n = len(dets)
     if n == 0:
         return []
-    order = dets[:, 7].argsort()[::-1]
+    # the reference leaves the order among EQUAL scores to numpy's default argsort (undefined above 16 elements); the
+    # project defines it: a stable ascending sort read backwards, i.e. among equal scores the LATER row comes first
+    # ("NMS tie order"; csrc/box_iou.hip nms_kernel sorts with the same rule)
+    order = dets[:, 7].argsort(kind="stable")[::-1]
     corners = boxes3d2corners(dets[:, :7])
     lo, hi = corners.min(1), corners.max(1)
     suppressed = np.zeros(n, dtype=bool)

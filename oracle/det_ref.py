@@ -170,9 +170,14 @@ def size_decode(off, mean_size, cid):
     return sel * ex + ex
 
 
-def loss_tail(cls_raw, reg_raw, data, nb=12, ncls=None, mean_size=None):
+def loss_tail(cls_raw, reg_raw, data, nb=12, ncls=None, mean_size=None, head_bin=None):
     """Returns dict of the 8 loss scalars of models/det_base.py:505-514 (ncls / mean_size default to the dataset the head
-    width belongs to: 39 columns KITTI, 67 SUN-RGBD)."""
+    width belongs to: 39 columns KITTI, 67 SUN-RGBD).
+    head_bin (B,) int64, optional: the heading bin of each frustum's label, for labels that sit ON a bin edge, where a
+    float32 and a float64 evaluation of angle_encode legitimately pick different neighbours; the residual is then the
+    wrapped angular distance of the label to THAT bin's centre (== angle_encode's wherever the bins agree).
+    A batch without a foreground row (the reference asserts on it, det_base.py:416): the foreground terms are 0, as the
+    kernel reports them."""
     if ncls is None:
         ncls = (reg_raw.shape[1] - 3 - 2 * nb) // 4
     if mean_size is None:
@@ -194,6 +199,10 @@ def loss_tail(cls_raw, reg_raw, data, nb=12, ncls=None, mean_size=None):
     pt = p[torch.arange(len(t)), t]
     cls_loss = (-alpha * (1 - pt) ** 2 * torch.log(pt + 1e-14)).sum() / (nfg + 1e-14)
 
+    if fg.numel() == 0:
+        z = cls_loss * 0
+        return {"total_loss": cls_loss, "cls_loss": cls_loss, "center_loss": z, "head_cls_loss": z, "head_res_loss": z,
+                "size_cls_loss": z, "size_res_loss": z, "corners_loss": z}
     o = out[fg]
     r2 = ref2[fg]
     center, hs, hr = o[:, 0:3], o[:, 3:3 + nb], o[:, 3 + nb:3 + 2 * nb]
@@ -205,7 +214,13 @@ def loss_tail(cls_raw, reg_raw, data, nb=12, ncls=None, mean_size=None):
     sc_lab = data["size_class"].expand(-1, L2).reshape(-1)[fg]
 
     center_loss = huber(torch.norm(c_lab - r2 - center, 2, dim=-1), 3.0)
-    hc, hres = angle_encode(h_lab, nb)
+    if head_bin is None:
+        hc, hres = angle_encode(h_lab, nb)
+    else:
+        hc = head_bin.view(-1, 1).expand(-1, L2).reshape(-1)[fg]
+        per = 2 * np.pi / nb
+        dlt = h_lab % (2 * np.pi) - hc.to(h_lab.dtype) * per
+        hres = ((dlt + np.pi) % (2 * np.pi) - np.pi) / (per / 2)
     head_cls = F.cross_entropy(hs, hc)
     head_res = huber(torch.gather(hr, 1, hc.view(-1, 1)).squeeze(1) - hres, 1.0)
     size_cls = F.cross_entropy(ss, sc_lab)

@@ -24,6 +24,9 @@ CASES = [
     ("test_gpu_grouping", "test_golden_full", ("refine_b4_n512",)),
     ("test_gpu_grouping", "test_golden_sha", ("car_b32_n1024",)),
     ("test_gpu_grouping", "test_golden_sha", ("people_b2_n512",)),
+    ("test_gpu_grouping", "test_golden_sha", ("people_b32_n1024",)),
+    ("test_gpu_grouping", "test_golden_sha", ("refine_b32_n512",)),
+    ("test_gpu_grouping", "test_golden_sha", ("sunrgbd_b32_n2048",)),
     ("test_gpu_grouping", "test_ragged_shapes", (1, 1, 1, 1, 0.5)),
     ("test_gpu_grouping", "test_ragged_shapes", (2, 63, 5, 7, 0.3)),
     ("test_gpu_grouping", "test_ragged_shapes", (2, 65, 17, 64, 0.3)),
@@ -93,6 +96,75 @@ CASES = [
     ("test_gpu_model", "test_fused_convnet_matches_module_path", ("people_b2_n512",)),
     ("test_gpu_model", "test_gradients_vs_fp64_oracle", ()),
     ("test_gpu_model", "test_fp16_operand_overflow_raises_the_flag", ()),
+    # the loss tail / IoU metrics / decode / NMS off the fixture regime: every case of the two modules
+    ("test_gpu_loss_tail_regimes", "test_generator_terminates_and_float32_oracle_error", ()),
+    ("test_gpu_loss_tail_regimes", "test_fixture_census_is_printed", ()),
+    ("test_gpu_loss_tail_regimes", "test_loss_tail_regimes", (1, 1, 3)),
+    ("test_gpu_loss_tail_regimes", "test_loss_tail_regimes", (1, 2, 3)),
+    ("test_gpu_loss_tail_regimes", "test_loss_tail_regimes", (2, 1, 3)),
+    ("test_gpu_loss_tail_regimes", "test_loss_tail_regimes", (1, 3, 3)),
+    ("test_gpu_loss_tail_regimes", "test_loss_tail_regimes", (3, 1, 3)),
+    ("test_gpu_loss_tail_regimes", "test_loss_tail_regimes", (7, 9, 3)),
+    ("test_gpu_loss_tail_regimes", "test_loss_tail_regimes", (4, 16, 3)),
+    ("test_gpu_loss_tail_regimes", "test_loss_tail_regimes", (5, 13, 3)),
+    ("test_gpu_loss_tail_regimes", "test_loss_tail_regimes", (127, 1, 3)),
+    ("test_gpu_loss_tail_regimes", "test_loss_tail_regimes", (2, 64, 3)),
+    ("test_gpu_loss_tail_regimes", "test_loss_tail_regimes", (3, 43, 3)),
+    ("test_gpu_loss_tail_regimes", "test_loss_tail_regimes", (149, 7, 3)),
+    ("test_gpu_loss_tail_regimes", "test_loss_tail_regimes", (32, 140, 3)),
+    ("test_gpu_loss_tail_regimes", "test_loss_tail_regimes", (33, 140, 3)),
+    ("test_gpu_loss_tail_regimes", "test_loss_tail_regimes", (10, 252, 3)),
+    ("test_gpu_loss_tail_regimes", "test_loss_tail_label_extremes", ("nfg0", 3)),
+    ("test_gpu_loss_tail_regimes", "test_loss_tail_label_extremes", ("allfg", 3)),
+    ("test_gpu_loss_tail_regimes", "test_loss_tail_label_extremes", ("allignored", 3)),
+    ("test_gpu_loss_tail_regimes", "test_loss_tail_label_extremes", ("lastfg", 3)),
+    ("test_gpu_loss_tail_regimes", "test_scratch_is_ready_for_the_next_launch", (3,)),
+    ("test_gpu_loss_tail_regimes", "test_iou_metrics_scratch_resets_between_launches", (3,)),
+    ("test_gpu_loss_tail_regimes", "test_loss_tail_regimes", (1, 1, 10)),
+    ("test_gpu_loss_tail_regimes", "test_loss_tail_regimes", (1, 2, 10)),
+    ("test_gpu_loss_tail_regimes", "test_loss_tail_regimes", (2, 1, 10)),
+    ("test_gpu_loss_tail_regimes", "test_loss_tail_regimes", (1, 3, 10)),
+    ("test_gpu_loss_tail_regimes", "test_loss_tail_regimes", (3, 1, 10)),
+    ("test_gpu_loss_tail_regimes", "test_loss_tail_regimes", (7, 9, 10)),
+    ("test_gpu_loss_tail_regimes", "test_loss_tail_regimes", (4, 16, 10)),
+    ("test_gpu_loss_tail_regimes", "test_loss_tail_regimes", (5, 13, 10)),
+    ("test_gpu_loss_tail_regimes", "test_loss_tail_regimes", (127, 1, 10)),
+    ("test_gpu_loss_tail_regimes", "test_loss_tail_regimes", (2, 64, 10)),
+    ("test_gpu_loss_tail_regimes", "test_loss_tail_regimes", (3, 43, 10)),
+    ("test_gpu_loss_tail_regimes", "test_loss_tail_regimes", (149, 7, 10)),
+    ("test_gpu_loss_tail_regimes", "test_loss_tail_regimes", (32, 140, 10)),
+    ("test_gpu_loss_tail_regimes", "test_loss_tail_regimes", (33, 140, 10)),
+    ("test_gpu_loss_tail_regimes", "test_loss_tail_regimes", (10, 252, 10)),
+    ("test_gpu_loss_tail_regimes", "test_loss_tail_label_extremes", ("nfg0", 10)),
+    ("test_gpu_loss_tail_regimes", "test_loss_tail_label_extremes", ("allfg", 10)),
+    ("test_gpu_loss_tail_regimes", "test_loss_tail_label_extremes", ("allignored", 10)),
+    ("test_gpu_loss_tail_regimes", "test_loss_tail_label_extremes", ("lastfg", 10)),
+    ("test_gpu_loss_tail_regimes", "test_scratch_is_ready_for_the_next_launch", (10,)),
+    ("test_gpu_loss_tail_regimes", "test_iou_metrics_scratch_resets_between_launches", (10,)),
+    ("test_gpu_box_edges", "test_iou_family_closed_forms_hold_for_the_oracle", ()),
+    ("test_gpu_box_edges", "test_iou_pair_families_at_depth", ()),
+    ("test_gpu_box_edges", "test_decode_shapes", (1, 1, 3, 64)),
+    ("test_gpu_box_edges", "test_decode_shapes", (1, 255, 3, 64)),
+    ("test_gpu_box_edges", "test_decode_shapes", (1, 256, 3, 64)),
+    ("test_gpu_box_edges", "test_decode_shapes", (1, 257, 3, 64)),
+    ("test_gpu_box_edges", "test_decode_shapes", (3, 700, 3, 64)),
+    ("test_gpu_box_edges", "test_decode_ties_and_selection_branches", (3, 64)),
+    ("test_gpu_box_edges", "test_decode_shapes", (1, 1, 10, 128)),
+    ("test_gpu_box_edges", "test_decode_shapes", (1, 255, 10, 128)),
+    ("test_gpu_box_edges", "test_decode_shapes", (1, 256, 10, 128)),
+    ("test_gpu_box_edges", "test_decode_shapes", (1, 257, 10, 128)),
+    ("test_gpu_box_edges", "test_decode_shapes", (3, 700, 10, 128)),
+    ("test_gpu_box_edges", "test_decode_ties_and_selection_branches", (10, 128)),
+    ("test_gpu_box_edges", "test_nms_sizes_ties_and_units", ("small_r16",)),
+    ("test_gpu_box_edges", "test_nms_sizes_ties_and_units", ("r1_novalid",)),
+    ("test_gpu_box_edges", "test_nms_sizes_ties_and_units", ("r300_n1000",)),
+    ("test_gpu_box_edges", "test_nms_sizes_ties_and_units", ("r300_novalid",)),
+    ("test_gpu_box_edges", "test_nms_sizes_ties_and_units", ("r1024_n4096_4097",)),
+    ("test_gpu_box_edges", "test_nms_sizes_ties_and_units", ("r1024_novalid_4096",)),
+    ("test_gpu_box_edges", "test_nms_sizes_ties_and_units", ("topk_1",)),
+    ("test_gpu_box_edges", "test_nms_sizes_ties_and_units", ("topk_below_kept",)),
+    ("test_gpu_box_edges", "test_nms_duplicates_and_tie_order", ()),
+    ("test_gpu_box_edges", "test_fast_nms_equals_cube_nms", ()),
 ]
 
 

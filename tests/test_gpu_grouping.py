@@ -6,6 +6,7 @@ import pytest
 import torch
 
 from oracle import grouping
+from oracle.det_ref import NSAMPLE_SUNRGBD
 from helpers import load_golden, golden_inputs, NSAMPLE, adversarial_grouping_cases
 
 pytestmark = pytest.mark.gpu
@@ -35,12 +36,15 @@ def test_golden_full(case):
         assert np.array_equal(idx, g["idx%d" % (s + 1)].astype(np.int64))
 
 
-@pytest.mark.parametrize("case", ["car_b32_n1024", "people_b2_n512"])
+@pytest.mark.parametrize("case", ["car_b32_n1024", "people_b2_n512", "people_b32_n1024", "refine_b32_n512",
+                                  "sunrgbd_b32_n2048"])
 def test_golden_sha(case):
     g = load_golden(case)
     d = golden_inputs(g)
-    for s in range(4):
-        idx, cnt = _gpu(float(g["meta_strides"][s]), NSAMPLE[s], d["point_cloud"], d["center_ref%d" % (s + 1)])
+    nscale = len(g["meta_strides"])                 # 5 for SUN-RGBD, with its own nsample table
+    nsample = NSAMPLE if nscale == 4 else NSAMPLE_SUNRGBD
+    for s in range(nscale):
+        idx, cnt = _gpu(float(g["meta_strides"][s]), nsample[s], d["point_cloud"], d["center_ref%d" % (s + 1)])
         assert np.array_equal(cnt, g["cnt%d" % (s + 1)])
         assert hashlib.sha256(np.ascontiguousarray(idx).tobytes()).hexdigest() == str(g["idx%d_sha" % (s + 1)])
 

@@ -65,14 +65,45 @@ def test_decode_fallback_and_filter():
     assert idx == [] and rows.shape == (0, 8)                    # too-small boxes are dropped
 
 
-@pytest.fixture(scope="module")
-def host_lib():
+def _cpu_has_fma():
+    try:
+        with open("/proc/cpuinfo") as f:
+            return " fma " in f.read().replace("\n", " ")
+    except OSError:
+        return False
+
+
+@pytest.fixture(scope="module", params=["off", "fast"])
+def host_lib(request):
+    """The harness twice: without contraction, and contracted to fused multiply-adds as the device build is (-mfma where the
+    CPU has it; without it the second build repeats the first), so the coincident-edge pairs -- a signed distance of exactly
+    0 without contraction, a rounding residue of either sign with it -- are seen both ways without a GPU."""
     out = os.path.join(HERE, "host_harness", "_build")
     os.makedirs(out, exist_ok=True)
-    so = os.path.join(out, "libbox_iou_host.so")
+    so = os.path.join(out, "libbox_iou_host_%s.so" % request.param)
     src = os.path.join(HERE, "host_harness", "box_iou_host.cpp")
-    subprocess.check_call(["g++", "-O2", "-ffp-contract=off", "-shared", "-fPIC", src, "-o", so])
+    flags = ["-ffp-contract=" + request.param] + (["-mfma"] if request.param == "fast" and _cpu_has_fma() else [])
+    subprocess.check_call(["g++", "-O2"] + flags + ["-shared", "-fPIC", src, "-o", so])
     return ctypes.CDLL(so)
+
+
+def test_device_clip_core_families_at_depth_on_host(host_lib):
+    """The box families of tests/test_gpu_box_edges.py (coincident / collinear edges, 40 : 1 boxes, sizes of 1e-2 to 50 m,
+    heading differences of 1e-4 rad) moved to depths of 5 to 80 m: csrc/box_iou.h in float32 on the float32 corners vs the
+    float64 oracle on the same corners, at the GPU suite's bar of 5e-5.  (On absolute coordinates the clip core missed it by
+    3.5e-4 at 40 m and 7.5e-4 at 80 m for car-sized boxes, and entirely for boxes of a centimetre; relative to a vertex of
+    the first box it measures 2e-7 to 5e-7 at every depth, with and without contraction.)"""
+    from test_gpu_box_edges import DEPTHS, IOU_BAR, iou_family_arrays
+    fp = ctypes.POINTER(ctypes.c_float)
+    for x, z in DEPTHS:
+        a, b, ca, cb, exp, closed, names = iou_family_arrays(x, z)
+        ca, cb = np.ascontiguousarray(ca), np.ascontiguousarray(cb)
+        out = np.zeros((len(a), 2), dtype=np.float32)
+        host_lib.host_iou_from_corners(ca.ctypes.data_as(fp), cb.ctypes.data_as(fp), len(a), out.ctypes.data_as(fp))
+        err = np.abs(out - exp).max(1)
+        i = int(err.argmax())
+        print("host clip core at x %+.0f z %.0f m: worst %.2e (%s)" % (x, z, err[i], names[i]))
+        assert err[i] < IOU_BAR, (x, z, names[i], out[i], exp[i])
 
 
 def test_device_clip_core_arithmetic_on_host(host_lib):
