@@ -59,6 +59,11 @@ class PnWs(ctypes.Structure):
                 ("partial_both", ctypes.c_int32)]
 
 
+class PnInferWs(ctypes.Structure):
+    """fcn_pn_infer_ws: the folded parameters of one scale's single-launch inference forward."""
+    _fields_ = [("w1f", c_fp), ("wenc", c_fp), ("shift", c_fp)]
+
+
 class InpDesc(ctypes.Structure):
     _fields_ = [("B", ctypes.c_int32), ("N", ctypes.c_int32), ("pt_stride", ctypes.c_int32), ("L", ctypes.c_int32 * 4),
                 ("stride", ctypes.c_double * 4), ("max_depth", ctypes.c_double),
@@ -77,7 +82,7 @@ class InpRefineDesc(ctypes.Structure):
 
 
 EXPORTS = ("fcn_arch", "fcn_build_hash", "fcn_stat_replicas", "fcn_query_depth_point_f32", "fcn_query_depth_point_multi_f32", "fcn_pn_wgrad_rows", "fcn_pn_compact", "fcn_pn_group_compact", "fcn_pn_group_compact2",
-           "fcn_pn_pack_weights", "fcn_pn_pack_weights_all", "fcn_pn_forward", "fcn_pn_backward", "fcn_pn_backward2", "fcn_pn_backward3", "fcn_pn_backward_dense", "fcn_pn_conv_fwd", "fcn_det_loss_tail", "fcn_det_loss_tail_rows", "fcn_det_loss_tail_rows2", "fcn_det_iou_metrics",
+           "fcn_pn_pack_weights", "fcn_pn_pack_weights_all", "fcn_pn_infer_fold", "fcn_pn_infer", "fcn_pn_forward", "fcn_pn_backward", "fcn_pn_backward2", "fcn_pn_backward3", "fcn_pn_backward_dense", "fcn_pn_conv_fwd", "fcn_det_loss_tail", "fcn_det_loss_tail_rows", "fcn_det_loss_tail_rows2", "fcn_det_iou_metrics",
            "fcn_det_loss_tail_scratch_floats", "fcn_adam_step_f32", "fcn_sgd_step_f32", "fcn_adam_step_slots", "fcn_prepare_inputs", "fcn_prepare_inputs_refine", "fcn_prepare_inputs_sunrgbd", "fcn_stamp", "fcn_stream_capture_id",
            "fcn_convnet_sizes", "fcn_convnet_logits_ld", "fcn_convnet_pack", "fcn_convnet_forward", "fcn_convnet_forward2",
            "fcn_convnet_backward", "fcn_box3d_iou_pair_f32", "fcn_decode_detections", "fcn_rotate_nms_3d")
@@ -137,6 +142,11 @@ def lib():
     L.fcn_pn_forward.restype = ctypes.c_int
     L.fcn_pn_forward.argtypes = [ctypes.POINTER(PnDesc), ctypes.POINTER(PnParams), c_fp, c_fp,
                                  ctypes.POINTER(PnWs), c_fp, c_fp]
+    if hasattr(L, "fcn_pn_infer") or "FCN_LIB_NAME" not in os.environ:     # (A/B builds of older kernel sources lack them)
+        L.fcn_pn_infer_fold.restype = ctypes.c_int
+        L.fcn_pn_infer_fold.argtypes = [ctypes.c_int, c_fp, c_fp, c_fp, c_fp, c_fp]
+        L.fcn_pn_infer.restype = ctypes.c_int
+        L.fcn_pn_infer.argtypes = [ctypes.POINTER(PnDesc), c_fp, c_fp, ctypes.POINTER(PnWs), ctypes.POINTER(PnInferWs), c_fp, c_fp]
     L.fcn_pn_backward.restype = ctypes.c_int
     L.fcn_pn_backward.argtypes = [ctypes.POINTER(PnDesc), ctypes.POINTER(PnParams), c_fp,
                                   ctypes.POINTER(PnWs), c_fp * 3, c_fp * 3, c_fp * 3, c_fp]

@@ -1019,3 +1019,7 @@ extern "C" int fcn_pn_conv_fwd(const fcn_pn_desc *d, const fcn_pn_params *p, con
     a.stat = with_stats ? st3 : nullptr; a.CIN = C2; a.COUT = C3;
     return launch_fwd_gemm<1>(a, B, d->precision, st);
 }
+
+// ------------------------------------------------------------------------------------------------
+// eval-mode single-pass forward (BatchNorm folded): fcn_pn_infer_fold / fcn_pn_infer
+#include "pn_infer.h"

@@ -62,6 +62,17 @@ class PointNetModule(nn.Module):
         init_params([self.conv1[1], self.conv2[1], self.conv3[1]], 1)
         self._pool = WorkspacePool()
         self.bn_frozen = False
+        self.fused_eval = os.environ.get("FCN_FUSED_EVAL", "0") != "0"
+
+    def fuse_eval(self, flag=True):
+        """Single-launch inference forward (module state like freeze_bn, not in the state_dict; initial value from FCN_FUSED_EVAL,
+        default off): where this scale runs on its running statistics without an autograd graph -- eval() under no_grad, or without
+        trainable parameters -- and the operand precision is a 16-bit one, BatchNorm is folded into the weights and ONE launch takes
+        the entries to the pooled features (fcn_pn_infer).  Results differ from the layered eval path by fp32 rounding only.
+        Everything else -- train(), freeze_bn() with gradients, the fp32 precision mode, forward()'s dense output -- is untouched.
+        Returns self."""
+        self.fused_eval = bool(flag)
+        return self
 
     def freeze_bn(self, flag=True):
         """Frozen BatchNorm (module state like .training, not in the state_dict): in train() and eval() alike the three BatchNorms
@@ -87,7 +98,8 @@ class PointNetModule(nn.Module):
         bn = self.conv1[1]
         feat, _, _ = pointnet_pooled(self._pool, self.dist, self.nsample, _bn_mode(self), bn.eps,
                                      bn_momentum(bn),
-                                     pc.contiguous(), new_pc.contiguous(), one_hot_vec, bufs, params, nlc=nlc)
+                                     pc.contiguous(), new_pc.contiguous(), one_hot_vec, bufs, params, nlc=nlc,
+                                     fuse_eval=self.fused_eval)
         return feat
 
     def launch_pooled(self, pc, new_pc, one_hot_vec=None, nlc=False):
@@ -96,7 +108,8 @@ class PointNetModule(nn.Module):
         bn = self.conv1[1]
         return launch_pooled(self._pool, self.dist, self.nsample, _bn_mode(self), bn.eps,
                              bn_momentum(bn),
-                             pc.contiguous(), new_pc.contiguous(), one_hot_vec, bufs, params, nlc=nlc)
+                             pc.contiguous(), new_pc.contiguous(), one_hot_vec, bufs, params, nlc=nlc,
+                             fuse_eval=self.fused_eval)
 
     def prepare_pooled(self, pc, new_pc, one_hot_vec=None, nlc=False):
         """Workspace / descriptor of this scale for the fused front (pointnet_fused.group_compact + launch_prepared)."""
@@ -104,7 +117,8 @@ class PointNetModule(nn.Module):
         params, bufs = self._param_pack()
         bn = self.conv1[1]
         return prepare_pooled(self._pool, self.dist, self.nsample, _bn_mode(self), bn.eps, bn_momentum(bn),
-                              pc.contiguous(), new_pc.contiguous(), one_hot_vec, bufs, params, nlc=nlc)
+                              pc.contiguous(), new_pc.contiguous(), one_hot_vec, bufs, params, nlc=nlc,
+                              fuse_eval=self.fused_eval)
 
     def attach_pooled(self, handle):
         feat, _, _ = attach_pooled(self._pool, handle)
@@ -112,13 +126,13 @@ class PointNetModule(nn.Module):
 
     def front_signature(self, nlc=False):
         """Everything a prepared handle (prepare_pooled) FREEZES besides the input tensors: the configuration tuple (BatchNorm mode,
-        need_grad, BatchNorm eps / momentum, layout), the operand precision and where the parameters and BatchNorm buffers live.
+        need_grad, BatchNorm eps / momentum, layout, the fuse_eval flag), the operand precision and where the parameters and BatchNorm buffers live.
         A prefetched front is only consumed by a forward that would have prepared the same handle."""
         from .pointnet_fused import _cfg_tuple
         from . import precision as _precision
         params, bufs = self._param_pack()
         bn = self.conv1[1]
-        cfgt = _cfg_tuple(self.dist, self.nsample, _bn_mode(self), bn.eps, bn_momentum(bn), params, nlc)
+        cfgt = _cfg_tuple(self.dist, self.nsample, _bn_mode(self), bn.eps, bn_momentum(bn), params, nlc, self.fused_eval)
         return (cfgt, _precision.code(), tuple(t.data_ptr() for t in params), tuple(t.data_ptr() for b in bufs for t in b))
 
     def forward(self, pc, feat, new_pc=None):
@@ -220,6 +234,12 @@ class PointNetFeat(nn.Module):
         """PointNetModule.freeze_bn on every scale.  Returns self."""
         for net in self.nets:
             net.freeze_bn(flag)
+        return self
+
+    def fuse_eval(self, flag=True):
+        """PointNetModule.fuse_eval on every scale.  Returns self."""
+        for net in self.nets:
+            net.fuse_eval(flag)
         return self
 
     @property
@@ -566,6 +586,12 @@ class PointNetDet(nn.Module):
         model.conv_net.freeze_bn() freeze one part only.  Returns self."""
         self.feat_net.freeze_bn(flag)
         self.conv_net.freeze_bn(flag)
+        return self
+
+    def fuse_eval(self, flag=True):
+        """Single-launch inference forward of the PointNet scales (PointNetModule.fuse_eval): taken by forward() under eval() without
+        an autograd graph and by detect().  Opt-in; training and frozen-BatchNorm fine-tuning are untouched.  Returns self."""
+        self.feat_net.fuse_eval(flag)
         return self
 
     def _differentiates(self):

@@ -10,7 +10,7 @@ import os
 import torch
 
 from . import _native
-from ._native import PnDesc, PnParams, PnWs
+from ._native import PnDesc, PnParams, PnWs, PnInferWs
 from .query_depth_point import query_depth_point
 from . import precision as _precision
 
@@ -87,6 +87,18 @@ class Workspace:
                       # of 8, bit-identical gradients) -- _mid_launch() below says where that pays
                       (1 if _mid_launch(B, L, K, C3) else (0 if os.environ.get("FCN_PN_TAIL", "1") == "0" else 2)) if need_grad else 0)
 
+    def infer_ws(self):
+        """The folded parameters of the single-launch inference forward (fcn_pn_infer_ws), allocated on first use and kept with the
+        workspace -- and so with the scale's pool."""
+        if getattr(self, "_infer", None) is None:
+            _, _, _, _, C1, C2, C3, _ = self.key
+            dev = self.woff.device
+            self.w1f = torch.empty((4 * C1,), dtype=torch.float32, device=dev)
+            self.wfold = torch.empty((C2 * C1 + C3 * C2,), dtype=torch.float32, device=dev)
+            self.shift = torch.empty((2 * (C2 + C3),), dtype=torch.float32, device=dev)      # t2, t3, epilogue scales
+            self._infer = PnInferWs(self.w1f.data_ptr(), self.wfold.data_ptr(), self.shift.data_ptr())
+        return self._infer
+
     @staticmethod
     def stored(t, precision_code):
         """fp32 view of one of the big intermediates (y2, y3, dy3, dz2) as the kernels of `precision_code` stored it: fp32, or --
@@ -152,6 +164,7 @@ def _acquire(pool, cfgt, pc, ref, one_hot, bufs, plist, need_grad):
     """Workspace, descriptor and C parameter struct of one scale's forward (no launch)."""
     dist, K, training, eps, momentum = cfgt[:5]
     nlc = bool(cfgt[6]) if len(cfgt) > 6 else False
+    fuse = bool(cfgt[7]) if len(cfgt) > 7 else False
     W1, g1, b1, W2, g2, b2, W3, g3, b3 = plist
     B, _, N = pc.shape
     Lw = ref.shape[2]
@@ -170,7 +183,56 @@ def _acquire(pool, cfgt, pc, ref, one_hot, bufs, plist, need_grad):
     oh = None if (one_hot is None or nlc) else one_hot.detach().contiguous().float()
     return {"ws": ws, "desc": desc, "params": params, "Wc": Wc, "gs": gs, "bs": bs, "oh": oh, "nlc": nlc, "nvec": nvec,
             "ref": ref, "dist": float(dist), "dims": (B, Lw, C3), "dev": dev,
+            "fused_eval": fuse and fused_eval_supported(int(training), desc.precision, C2),
             "bufs": bufs}       # (the C struct holds raw pointers to the running statistics: the handle keeps their tensors alive)
+
+
+INFER_MAX_C2 = 256      # csrc/pn_infer.h PNI_MAXC2: the h2 tile of a workgroup lives in LDS
+
+
+def fused_eval_supported(mode, precision_code, C2):
+    """Whether fcn_pn_infer takes a scale: running statistics (nothing saved, no autograd graph), a 16-bit operand precision (the
+    fp32 reference mode keeps the layered path) and an h2 tile that fits the LDS.  A loaded library without the kernels (an
+    FCN_LIB_NAME build of older sources) is an error, not a fallback: the caller opted in."""
+    if not (int(mode) == _native.BN_RUNNING and precision_code != _precision.CODES["f32"] and C2 <= INFER_MAX_C2):
+        return False
+    if not hasattr(_native.lib(), "fcn_pn_infer"):
+        raise RuntimeError("fuse_eval is on, but the loaded native library has no fcn_pn_infer (built from older kernel "
+                           "sources?): rebuild it, or switch the flag off (fuse_eval(False) / FCN_FUSED_EVAL=0)")
+    return True
+
+
+def infer_fold(handles):
+    """fcn_pn_infer_fold for the prepared scales (one launch on the current stream): BatchNorm folded into the weights from the
+    running statistics as they are NOW -- it runs every forward, like the weight packing it replaces -- and the zero fill of the
+    feature buffers, which are allocated here."""
+    L = _native.lib()
+    n = len(handles)
+    dev = handles[0]["dev"]
+    for h in handles:
+        B, Lw, C3 = h["dims"]
+        h["feat"] = torch.empty((B, Lw, C3) if h["nlc"] else (B, C3 + h["nvec"], Lw), dtype=torch.float32, device=dev)
+    arr = lambda vals: (ctypes.c_void_p * n)(*vals)
+    with torch.cuda.device(dev):
+        _native.check(L.fcn_pn_infer_fold(n, arr([ctypes.addressof(h["desc"]) for h in handles]),
+                                          arr([ctypes.addressof(h["params"]) for h in handles]),
+                                          arr([ctypes.addressof(h["ws"].infer_ws()) for h in handles]),
+                                          arr([h["feat"].data_ptr() for h in handles]), _native.current_stream(dev)),
+                      "fcn_pn_infer_fold")
+
+
+def _run_infer(h, cnt, idx):
+    """fcn_pn_infer of a folded scale on the current stream -> the tuple _PointNetPooled keeps."""
+    L = _native.lib()
+    dev = h["dev"]
+    feat = h.pop("feat")
+    if getattr(torch.cuda.current_stream(dev), "cuda_stream", 0):       # (allocated on the stream that ran the fold)
+        feat.record_stream(torch.cuda.current_stream(dev))
+    with torch.cuda.device(dev):
+        _native.check(L.fcn_pn_infer(ctypes.byref(h["desc"]), cnt.data_ptr(), None if h["oh"] is None else h["oh"].data_ptr(),
+                                     ctypes.byref(h["ws"].c), ctypes.byref(h["ws"].infer_ws()), feat.data_ptr(),
+                                     _native.current_stream(dev)), "fcn_pn_infer")
+    return feat, idx, cnt, h["ws"], h["desc"], (h["Wc"], h["gs"], h["bs"], cnt, idx, h["oh"])
 
 
 def _run_forward(h, cnt, idx):
@@ -194,6 +256,9 @@ def _forward_impl(pool, cfgt, pc, ref, one_hot, bufs, plist, need_grad):
     with torch.cuda.device(h["dev"]):
         _native.check(L.fcn_pn_compact(ctypes.byref(h["desc"]), pc.data_ptr(), ref.data_ptr(), idx.data_ptr(),
                                        cnt.data_ptr(), ctypes.byref(h["ws"].c), _native.current_stream(h["dev"])), "fcn_pn_compact")
+    if h["fused_eval"]:
+        infer_fold([h])
+        return _run_infer(h, cnt, idx)
     return _run_forward(h, cnt, idx)
 
 
@@ -205,6 +270,18 @@ def group_compact(handles, pc, phase=3):
     L = _native.lib()
     n = len(handles)
     dev = pc.device
+    # single-launch inference (fuse_eval): all scales or none -- the front takes one set of launches for all of them.  Its
+    # weight-dependent part is fcn_pn_infer_fold instead of phase 2 (weight images + BN1 fold of the layered forward).
+    phase_all = phase == 3
+    fused = all(h.get("fused_eval") for h in handles)
+    if not fused:
+        for h in handles:
+            h["fused_eval"] = False
+    elif phase == 2:
+        infer_fold(handles)
+        return
+    elif phase == 3:
+        phase = 1
     arr = lambda vals: (ctypes.c_void_p * n)(*vals)
     descs = arr([ctypes.addressof(h["desc"]) for h in handles])
     params = arr([ctypes.addressof(h["params"]) for h in handles])
@@ -215,6 +292,10 @@ def group_compact(handles, pc, phase=3):
     with torch.cuda.device(dev):
         _native.check(L.fcn_pn_group_compact2(n, descs, params, pc.data_ptr(), refs, dz, wss, cnts, int(phase),
                                               _native.current_stream(dev)), "fcn_pn_group_compact2")
+    if fused:
+        if phase_all:
+            infer_fold(handles)
+        return
     if phase != 1:
         for h in handles:
             h["desc"].grouped = 1
@@ -335,16 +416,17 @@ class _PointNetPooled(torch.autograd.Function):
         return (None, None, None, None, None, None, None, None) + tuple(outs)
 
 
-def _cfg_tuple(dist, nsample, mode, eps, momentum, params, nlc):
+def _cfg_tuple(dist, nsample, mode, eps, momentum, params, nlc, fuse_eval=False):
     """mode: the BatchNorm mode (_native.BN_*; a bool is read as train / running).  A frozen forward that nothing will differentiate
-    takes the inference path (BN_RUNNING: the same statistics, nothing saved)."""
+    takes the inference path (BN_RUNNING: the same statistics, nothing saved).  fuse_eval: the caller opts in to the single-launch
+    inference forward (fcn_pn_infer) where the resulting mode is BN_RUNNING; part of the tuple, so of every front signature."""
     mode = int(mode)
     if mode not in (_native.BN_RUNNING, _native.BN_TRAIN, _native.BN_FROZEN):
         raise ValueError("unknown BatchNorm mode %r" % (mode,))
     need_grad = mode != _native.BN_RUNNING and torch.is_grad_enabled() and any(t.requires_grad for t in params)
     if mode == _native.BN_FROZEN and not need_grad:
         mode = _native.BN_RUNNING
-    return (float(dist), int(nsample), mode, float(eps), float(momentum), need_grad, bool(nlc))
+    return (float(dist), int(nsample), mode, float(eps), float(momentum), need_grad, bool(nlc), bool(fuse_eval))
 
 
 def _check_device(pc):
@@ -353,11 +435,11 @@ def _check_device(pc):
                            "(got a %s tensor); there is no CPU fallback" % pc.device)
 
 
-def prepare_pooled(pool, dist, nsample, training, eps, momentum, pc, ref, one_hot, bufs, params, nlc=False):
+def prepare_pooled(pool, dist, nsample, training, eps, momentum, pc, ref, one_hot, bufs, params, nlc=False, fuse_eval=False):
     """Step 1 of the fused front: acquire this scale's workspace / descriptor.  Call group_compact() on the handles of all
     scales (one launch), then launch_prepared() per scale on its own stream."""
     _check_device(pc)
-    cfgt = _cfg_tuple(dist, nsample, training, eps, momentum, params, nlc)
+    cfgt = _cfg_tuple(dist, nsample, training, eps, momentum, params, nlc, fuse_eval)
     h = _acquire(pool, cfgt, pc, ref, one_hot, bufs, params, cfgt[5])
     h["args"] = (cfgt, pc, ref, one_hot, bufs, params)
     return h
@@ -367,16 +449,16 @@ def launch_prepared(h):
     """fcn_pn_forward of a grouped scale on the current stream -> handle for attach_pooled()."""
     cfgt, pc, ref, one_hot, bufs, params = h["args"]
     with torch.no_grad():
-        launched = _run_forward(h, h["ws"].cnt, _empty_idx(h["dev"]))
+        launched = (_run_infer if h["fused_eval"] else _run_forward)(h, h["ws"].cnt, _empty_idx(h["dev"]))
     return (cfgt, pc, ref, one_hot, bufs, params, launched)
 
 
-def launch_pooled(pool, dist, nsample, training, eps, momentum, pc, ref, one_hot, bufs, params, nlc=False):
+def launch_pooled(pool, dist, nsample, training, eps, momentum, pc, ref, one_hot, bufs, params, nlc=False, fuse_eval=False):
     """Enqueues the forward kernels of one scale on the current stream WITHOUT creating the autograd node and returns a
     handle for attach_pooled().  Splitting the two lets a caller launch the scales heaviest-first while creating their
     nodes lightest-first -- autograd runs backward nodes in reverse creation order, so the backward is heaviest-first too."""
     _check_device(pc)
-    cfgt = _cfg_tuple(dist, nsample, training, eps, momentum, params, nlc)
+    cfgt = _cfg_tuple(dist, nsample, training, eps, momentum, params, nlc, fuse_eval)
     with torch.no_grad():
         launched = _forward_impl(pool, cfgt, pc, ref, one_hot, bufs, params, cfgt[5])
     return (cfgt, pc, ref, one_hot, bufs, params, launched)
@@ -389,11 +471,11 @@ def attach_pooled(pool, handle):
     return _PointNetPooled.apply(pool, cfgt, pc, ref, one_hot, bufs, gdst, launched, *params)
 
 
-def pointnet_pooled(pool, dist, nsample, training, eps, momentum, pc, ref, one_hot, bufs, params, nlc=False):
+def pointnet_pooled(pool, dist, nsample, training, eps, momentum, pc, ref, one_hot, bufs, params, nlc=False, fuse_eval=False):
     """params = (W1,g1,b1,W2,g2,b2,W3,g3,b3); bufs = ([rm1,rm2,rm3],[rv1,rv2,rv3],[nbt1,nbt2,nbt3]).
     nlc=True returns position-major (B, L, C3) features without the one-hot rows (input of the fused ConvFeatNet)."""
     _check_device(pc)
-    cfgt = _cfg_tuple(dist, nsample, training, eps, momentum, params, nlc)
+    cfgt = _cfg_tuple(dist, nsample, training, eps, momentum, params, nlc, fuse_eval)
     gdst = tuple(getattr(t, "_fcn_grad", None) for t in params)
     return _PointNetPooled.apply(pool, cfgt, pc, ref, one_hot, bufs, gdst, None, *params)
 

@@ -15,6 +15,8 @@
  *                               PointNetFeat.forward: gather, centre subtract, 3 x [Conv2d 1x1, BatchNorm2d,
  *                               ReLU], (cnt>0) mask, torch.max(.,-1), one-hot concat
  *                               models/det_base.py:75-101,134-157 (+ autograd of the same)
+ *   fcn_pn_infer_fold / fcn_pn_infer
+ *                               the same forward under model.eval() in one launch per scale (BatchNorm folded)
  *   fcn_convnet_forward/backward ConvFeatNet.forward + cls_out/reg_out (cuDNN/ATen in the reference),
  *                               models/det_base.py:196-224,367-368 (+ autograd of the same)
  *   fcn_convnet_pack / _forward2 the same forward with the weight re-packing split off and per-feature-map start events
@@ -261,6 +263,39 @@ int fcn_pn_backward_dense(const fcn_pn_desc *d, const fcn_pn_params *p, const fl
 int fcn_pn_backward3(const fcn_pn_desc *d, const fcn_pn_params *p, const float *dfeat,
                      const fcn_pn_ws *ws, float *dW[3], float *dgamma[3], float *dbeta[3],
                      void *stream, void *stream2, void *stream3, void *const *events);
+
+/* ---------------------------------------------------------------------------------------------
+ * Single-launch inference forward of one scale (csrc/pn_infer.h): with running statistics the three BatchNorms are affine maps
+ * known before the launch; they fold into the weights and one workgroup takes a 64-row tile of entries to pooled features
+ * without touching HBM in between.  Results differ from fcn_pn_forward in FCN_BN_RUNNING mode by fp32 rounding only (the scale
+ * is rounded into the weight instead of applied to the activation).
+ *   fcn_pn_infer_ws  caller-owned buffers of the folded parameters, all 16-byte aligned, rewritten by every fcn_pn_infer_fold.
+ *   fcn_pn_infer_fold  ONE small launch for nscale <= 8 scales: scale / shift of every BatchNorm from the running statistics
+ *                    (read, never written; num_batches_tracked is not touched), the folded weights into iws[s], and the zero
+ *                    fill of feat[s] (fcn_pn_infer publishes into it with atomic maxima: the fill must precede every tile and
+ *                    nothing else may write feat[s] in between).  All scales share eps.  p[s]->W[1], W[2] 16-byte aligned.
+ *   fcn_pn_infer     one launch: entries (ws->woff, ent, ewin, tiles as fcn_pn_compact / fcn_pn_group_compact[2] left them -- phase
+ *                    1 of the phased front is enough, the BN1 fold and weight images of phase 2 are not read) + cnt (B, L) ->
+ *                    feat, laid out by d->nlc exactly as fcn_pn_forward's (one_hot (B, nvec) rows appended when nlc = 0).
+ *                    Empty windows (cnt == 0) keep the fill value +0.0.  Bit-identical from run to run.  A non-finite GEMM
+ *                    output, in every precision, sets FCN_FLAG_NONFINITE in ws->flags (when non-NULL).
+ * Contract: d->training must be FCN_BN_RUNNING (FCN_E_BADARG otherwise); ws->y2, y3, pkey, stat, amax, gmax, bn, wenc may be
+ * NULL; widths as fcn_pn_forward (multiples of 64, C1 <= 512) except C2 <= 256 (FCN_E_LIMIT above: the h2 tile lives in LDS);
+ * L <= 8192, K <= 1024, B * L * K < 2^31.  Precisions: FCN_PREC_SPLIT, FCN_PREC_BF16, FCN_PREC_BF16_OPS (the two bf16 modes are
+ * identical here: nothing intermediate is stored).  FCN_PREC_F32 returns FCN_E_BADARG -- take fcn_pn_forward for it (the Python
+ * layer does).
+ * ------------------------------------------------------------------------------------------- */
+typedef struct fcn_pn_infer_ws {
+    float *w1f;                  /* 4*C1 floats: rows (s1*W1[c][0..2], t1[c])                                      */
+    float *wenc;                 /* C2*C1 + C3*C2 floats: diag(s2) W2, diag(s3) W3 (bf16 modes: W2, W3) in the forward
+                                    MFMA operand order                                                                 */
+    float *shift;                /* 2*(C2 + C3) floats: t2, t3, then the epilogue scales of conv2 / conv3 (ones in
+                                    FCN_PREC_SPLIT, s2, s3 in the bf16 modes, whose images hold the unscaled weights)  */
+} fcn_pn_infer_ws;
+int fcn_pn_infer_fold(int nscale, const fcn_pn_desc *const *d, const fcn_pn_params *const *p,
+                      const fcn_pn_infer_ws *const *iws, float *const *feat, void *stream);
+int fcn_pn_infer(const fcn_pn_desc *d, const int32_t *cnt, const float *one_hot, const fcn_pn_ws *ws,
+                 const fcn_pn_infer_ws *iws, float *feat, void *stream);
 
 /* Launches ONLY the conv GEMM of `layer` (2 or 3) on the state a previous fcn_pn_compact/fcn_pn_forward left in
  * ws: the unit the roofline figure in bench.py is measured on.  with_stats != 0 keeps the BN-statistics epilogue. */
