@@ -5,6 +5,7 @@
     from frustum_convnet_amd.config import cfg, merge_cfg_from_file
     from frustum_convnet_amd.train_state import FlatTrainState       # flat parameters / gradients / Adam moments
     from frustum_convnet_amd.inputs import InputBuilder              # batch construction on the device
+    from frustum_convnet_amd.cascade import TwoStageDetector         # first-stage boxes -> refine inputs -> second stage
 
 Nothing here imports torch or loads libfcn_hip.so eagerly: `_native.lib()` does on first use and raises ImportError
 when the library has not been built (`python -m frustum_convnet_amd.build`); there is no CPU fallback.

@@ -1,0 +1,105 @@
+"""The two-stage cascade on the device: first-stage boxes -> refinement-stage inputs (C-ABI fcn_refine_select_count / _fill,
+csrc/refine_select.h) and a thin driver over both stages.
+
+Reference: kitti/prepare_data_refine.py::extract_frustum_data_rgb_detection (:649-773) reads the first stage's result files,
+enlarges every predicted box by 1.2, selects the frame's LiDAR points inside it with scipy.spatial.Delaunay(...).find_simplex
+on the host -- once per box over the frame's whole point cloud -- and pickles them for datasets/provider_sample_refine.py.
+Here the selection is two HIP launches and the selected points go straight into RefineInputBuilder.build_device; between the
+stages the host reads the first stage's keep lists, D point counts and D predicted widths, and each of the two entry points
+reads the 2 * D candidate indices back to range-check them (five small reads that wait for the stream; no point data).  No CPU
+fallback.
+"""
+import numpy as np
+import torch
+
+from . import _native
+from .detect import _need_cuda
+
+
+def refine_candidates(frame_points, frame_off, dets, cand_row, cand_frame, ratio=1.2):
+    """frame_points (sum m_f, stride >= 3) float32 rect camera coordinates of F frames packed behind each other (columns from 3
+    on travel untouched), frame_off (F+1) int64 row offsets, dets (R,8) float32 label-format rows [tx,ty,tz,l,w,h,ry,score] as
+    decode_detections / PointNetDet.detect return them, cand_row (D) indices into dets, cand_frame (D) the frame of each --
+    device tensors (the two lists may be host sequences).  Every candidate box is enlarged by `ratio` about its centre.
+    Returns a dict: points (sum cnt, stride) the frame rows inside each enlarged box, candidate after candidate in frame order;
+    off (D+1) int64; pred_box3d (D,8,3), pred_angle (D), pred_size (D,3) fp64 (the enlarged box: corners in the order of
+    compute_box_3d_obj_array, ry, l/w/h); cnt (D) int32; score (D) float32 (column 7 of the candidates' rows) -- on the device --
+    and counts (D) int64 on the host: the one read between the two launches."""
+    _need_cuda(frame_points, "refine_candidates")
+    dev = frame_points.device
+    pts = frame_points.detach().contiguous().float()
+    if pts.dim() != 2 or pts.shape[1] < 3:
+        raise ValueError("refine_candidates: frame_points must be (n, >= 3), got %s" % (tuple(frame_points.shape),))
+    foff = torch.as_tensor(frame_off).to(device=dev, dtype=torch.int64).contiguous()
+    d8 = dets.detach().to(device=dev, dtype=torch.float32).contiguous()
+    if d8.dim() != 2 or d8.shape[1] != 8:
+        raise ValueError("refine_candidates: dets must be (R, 8), got %s" % (tuple(dets.shape),))
+    crow = torch.as_tensor(cand_row).to(device=dev, dtype=torch.int32).contiguous().view(-1)
+    cframe = torch.as_tensor(cand_frame).to(device=dev, dtype=torch.int32).contiguous().view(-1)
+    if crow.numel() != cframe.numel():
+        raise ValueError("refine_candidates: %d rows but %d frames" % (crow.numel(), cframe.numel()))
+    F, R, D, ps = int(foff.numel()) - 1, int(d8.shape[0]), int(crow.numel()), int(pts.shape[1])
+    f64 = dict(dtype=torch.float64, device=dev)
+    out = {"pred_box3d": torch.zeros((D, 8, 3), **f64), "pred_angle": torch.zeros((D,), **f64),
+           "pred_size": torch.zeros((D, 3), **f64), "cnt": torch.zeros((D,), dtype=torch.int32, device=dev)}
+    L = _native.lib()
+    args = (pts.data_ptr(), foff.data_ptr(), F, ps, d8.data_ptr(), R, crow.data_ptr(), cframe.data_ptr(), D, float(ratio))
+    with torch.cuda.device(dev):
+        _native.check(L.fcn_refine_select_count(*args, out["pred_box3d"].data_ptr(), out["pred_angle"].data_ptr(),
+                                                out["pred_size"].data_ptr(), out["cnt"].data_ptr(),
+                                                _native.current_stream(dev)), "fcn_refine_select_count")
+        counts = out["cnt"].cpu().numpy().astype(np.int64)                 # D integers: the size of `points`
+        off = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+        out["off"] = torch.from_numpy(off).to(dev, non_blocking=True)
+        out["points"] = torch.empty((int(off[-1]), ps), dtype=torch.float32, device=dev)
+        if off[-1] > 0:
+            _native.check(L.fcn_refine_select_fill(*args, out["off"].data_ptr(), out["points"].data_ptr(),
+                                                   _native.current_stream(dev)), "fcn_refine_select_fill")
+    out["score"] = d8[:, 7].index_select(0, crow.to(torch.int64)) if D else d8[:0, 7]
+    out["counts"] = counts
+    return out
+
+
+class TwoStageDetector:
+    """stage1, stage2: two PointNetDet models in eval mode, each built by the caller under its own configuration (cfg is
+    global: build one, then the other); refine_builder: the RefineInputBuilder of the second stage's configuration."""
+
+    def __init__(self, stage1, stage2, refine_builder):
+        self.stage1, self.stage2, self.refine_builder = stage1, stage2, refine_builder
+
+    def detect(self, data_dicts, frame_points, frame_off, frustum_frame, types, method, thresh, unit_group=None,
+               num_groups=None, top_k=300, ratio=1.2, draws=None):
+        """data_dicts: the first stage's batch of B frustums; frame_points / frame_off: the points to search, per frame (see
+        refine_candidates); frustum_frame (B) the frame of each frustum and types (B) its class name (host sequences);
+        method / thresh: as PointNetDet.detect, for both stages; unit_group (B) / num_groups: the (frame, class) group of
+        each frustum (default: every frustum its own) -- a second-stage unit inherits its frustum's group.
+        Steps: stage1.detect -> keep lists to the host -> refine_candidates -> refine_builder.build_device (draws: its
+        resample indices, for reproducible runs) -> stage2.detect.
+        Returns a dict: dets, valid, keep, cnt of the second stage (device), stage1_row (B2,) int64 (host) the first-stage
+        row of dets each second-stage unit refines, and stage1 = the first stage's (dets, valid, keep, cnt).  When the
+        first stage keeps nothing, or no kept box holds a point, the second-stage entries are None and stage1_row is empty."""
+        s1 = self.stage1.detect(data_dicts, unit_group=unit_group, num_groups=num_groups, method=method, thresh=thresh,
+                                top_k=top_k)
+        dets1, _, keep1, cnt1 = s1
+        L2 = int(data_dicts["center_ref2"].shape[2])
+        B = int(data_dicts["center_ref2"].shape[0])
+        keep_h, cnt_h = keep1.cpu().numpy(), cnt1.cpu().numpy()
+        rows = [keep_h[g, :c] for g, c in enumerate(cnt_h) if c > 0]
+        rows = np.concatenate(rows).astype(np.int64) if rows else np.zeros((0,), dtype=np.int64)
+        res = {"dets": None, "valid": None, "keep": None, "cnt": None, "stage1_row": rows[:0], "stage1": s1}
+        if len(rows) == 0:
+            return res
+        unit = rows // L2                                                    # the frustum each kept row came from
+        frame = np.asarray(frustum_frame, dtype=np.int64).reshape(B)[unit]
+        cands = refine_candidates(frame_points, frame_off, dets1, rows.astype(np.int32), frame.astype(np.int32), ratio)
+        batch = self.refine_builder.build_device(cands, [types[u] for u in unit], draws=draws)
+        kept = batch.pop("kept")
+        if len(kept) == 0:
+            return res
+        batch.pop("lens")
+        ug1 = np.arange(B) if unit_group is None else torch.as_tensor(unit_group).cpu().numpy().reshape(B)
+        ng = B if unit_group is None else (int(ug1.max()) + 1 if num_groups is None else num_groups)
+        ug2 = torch.from_numpy(ug1[unit[kept]].astype(np.int32)).to(dets1.device)
+        d2, v2, k2, c2 = self.stage2.detect(batch, unit_group=ug2, num_groups=ng, method=method, thresh=thresh, top_k=top_k)
+        res.update(dets=d2, valid=v2, keep=k2, cnt=c2, stage1_row=rows[kept])
+        return res

@@ -386,3 +386,7 @@ extern "C" int fcn_prepare_inputs_refine(const fcn_inp_refine_desc *d, const flo
     FCN_CHECK_LAUNCH();
     return 0;
 }
+
+// ------------------------------------------------------------------------------------------------
+// First-stage detections -> the raw points of the refinement stage (fcn_refine_select_count / _fill): csrc/refine_select.h
+#include "refine_select.h"

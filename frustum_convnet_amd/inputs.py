@@ -272,32 +272,11 @@ class RefineInputBuilder:
             raise NotImplementedError("RefineInputBuilder implements the cfg.DATA.RTC = True geometry only (every shipped "
                                       "refine cfg sets it: cfgs/refine_car.yaml, cfgs/refine_people.yaml)")
 
-    def build(self, records, draws=None, with_labels=True):
-        """records: dicts with REFINE_KEYS (points (n,>=3) float32 rect camera coordinates; box3d (8,3), heading, size (l,w,h)
-        of the label box; pred_box3d (8,3), pred_angle, pred_size of the first-stage prediction; type).  Returns the batch
-        dict on the device (+ 'lens' (B,4) int32: the per-sample window counts before padding)."""
-        if self.device.type != "cuda":
-            raise RuntimeError("frustum_convnet_amd: input construction is a HIP kernel (MI355X only); no CPU fallback")
+    def _launch(self, t, B, pt_stride, Lpad, with_labels):
+        """Allocates the outputs and enqueues fcn_prepare_inputs_refine on the device tensors `t` (raw, off, choice, pcorners,
+        pangle, psize; with labels also corners, heading, size, coin, normal): the part build() and build_device() share."""
         from ._native import InpRefineDesc
-        B, N = len(records), self.npoints
-        counts = [len(r["points"]) for r in records]
-        if draws is None:
-            draws = draw_refine(counts, N, self.random_flip and with_labels, self.random_shift and with_labels)
-        choice, coin, normal = draws
-        stride = int(records[0]["points"].shape[1])
-        raw = np.concatenate([np.ascontiguousarray(r["points"], dtype=np.float32) for r in records], 0)
-        off = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
-        f64 = lambda k, shape: np.stack([np.asarray(r[k], dtype=np.float64).reshape(shape) for r in records])
-        psize = f64("pred_size", (3,))
-        # batch maxima of len(np.arange(-w/2, w/2, s)): the padded widths of the outputs
-        Lpad = [int(max(len(np.arange(-w / 2.0, w / 2.0, s)) for w in psize[:, 1])) for s in self.strides]
-        dev = self.device
-        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev, non_blocking=True)
-        t = {"raw": up(raw), "off": up(off), "choice": up(np.asarray(choice, dtype=np.int32)),
-             "pcorners": up(f64("pred_box3d", (24,))), "pangle": up(f64("pred_angle", ())), "psize": up(psize)}
-        if with_labels:
-            t.update(corners=up(f64("box3d", (24,))), heading=up(f64("heading", ())), size=up(f64("size", (3,))),
-                     coin=up(np.asarray(coin, dtype=np.float64)), normal=up(np.asarray(normal, dtype=np.float64)))
+        dev, N = self.device, self.npoints
         f32 = dict(dtype=torch.float32, device=dev)
         out = {"point_cloud": torch.empty((B, 3, N), **f32), "rot_angle": torch.empty((B, 1), **f32),
                "ref_center": torch.empty((B, 3), **f32), "lens": torch.empty((B, 4), dtype=torch.int32, device=dev)}
@@ -307,7 +286,7 @@ class RefineInputBuilder:
                        box3d_size=torch.empty((B, 3), **f32))
         for s in range(4):
             out["center_ref%d" % (s + 1)] = torch.empty((B, 3, Lpad[s]), **f32)
-        desc = InpRefineDesc(B, N, stride, (ctypes.c_int32 * 4)(*Lpad), (ctypes.c_double * 4)(*self.strides),
+        desc = InpRefineDesc(B, N, pt_stride, (ctypes.c_int32 * 4)(*Lpad), (ctypes.c_double * 4)(*self.strides),
                              1 if (self.random_flip and with_labels) else 0, 1 if (self.random_shift and with_labels) else 0)
         refs = (ctypes.c_void_p * 4)(*[out["center_ref%d" % (s + 1)].data_ptr() for s in range(4)])
         p = lambda x: None if x is None else x.data_ptr()
@@ -321,13 +300,89 @@ class RefineInputBuilder:
                 _native.current_stream(dev)), "fcn_prepare_inputs_refine")
         for v in t.values():
             v.record_stream(torch.cuda.current_stream(dev))
+        return out
+
+    def _lpad(self, widths):
+        """Batch maxima of len(np.arange(-w/2, w/2, s)) over the predicted widths: the padded widths of the outputs."""
+        return [int(max(len(np.arange(-w / 2.0, w / 2.0, s)) for w in widths)) for s in self.strides]
+
+    def _one_hot(self, size_class):
+        oh = np.zeros((len(size_class), len(self.classes)), dtype=np.float32)
+        oh[np.arange(len(size_class)), size_class] = 1.0
+        return torch.from_numpy(oh).to(self.device, non_blocking=True)
+
+    def build_device(self, cands, types, prob=None, draws=None):
+        """The inference batch (build(..., with_labels=False)) straight from the device tensors of cascade.refine_candidates:
+        no point leaves the device.  cands: its dict (points, off, pred_box3d, pred_angle, pred_size, score on the device,
+        counts on the host); types: the class name of each of the D candidates; prob: their 'rgb_prob' (D) when it is not the
+        first-stage score (the reference's result files carry exactly that score); draws: (choice (B,N) int32, coin, normal)
+        for the B surviving candidates, or None to draw like draw_refine from their counts.
+        Candidates without a point are dropped before the launch (prepare_data_refine.py:739-741, lidar_point_threshold = 1);
+        'kept' (B,) int64 (host) lists the survivors' candidate indices.  The host reads D numbers here: the predicted widths,
+        which decide the padded window counts.  With no survivor the dict holds 'kept' alone."""
+        if self.device.type != "cuda":
+            raise RuntimeError("frustum_convnet_amd: input construction is a HIP kernel (MI355X only); no CPU fallback")
+        counts = np.asarray(cands["counts"], dtype=np.int64)
+        D, N = len(counts), self.npoints
+        if len(types) != D or (prob is not None and len(prob) != D):
+            raise ValueError("build_device: %d candidates, %d types%s" % (D, len(types), "" if prob is None else ", %d prob" % len(prob)))
+        kept = np.nonzero(counts > 0)[0]
+        B = len(kept)
+        if B == 0:
+            return {"kept": kept}
+        if draws is None:
+            draws = draw_refine(counts[kept], N, False, False)
+        dev = self.device
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev, non_blocking=True)
+        widths = cands["pred_size"][:, 1].cpu().numpy()                       # D numbers: the tensor shapes depend on them
+        sel = None if B == D else up(kept)
+        pick = lambda x: x.contiguous() if sel is None else x.index_select(0, sel).contiguous()
+        off = cands["off"]
+        t = {"raw": cands["points"], "choice": up(np.asarray(draws[0], dtype=np.int32)),
+             # the kernel reads a sample's first row only: the survivors' starts (+ the end of the last one, for the (B+1) form)
+             "off": off if sel is None else torch.cat([off.index_select(0, sel), off[int(kept[-1]) + 1:int(kept[-1]) + 2]]),
+             "pcorners": pick(cands["pred_box3d"]), "pangle": pick(cands["pred_angle"]), "psize": pick(cands["pred_size"])}
+        out = self._launch(t, B, int(cands["points"].shape[1]), self._lpad(widths[kept]), False)
+        if self.one_hot:
+            out["one_hot"] = self._one_hot([self.classes.index(types[i]) for i in kept])
+        if prob is None:
+            out["rgb_prob"] = pick(cands["score"]).to(torch.float32).reshape(B, 1)
+        else:
+            out["rgb_prob"] = up(np.asarray(prob, dtype=np.float32)[kept].reshape(B, 1))
+        out["kept"] = kept
+        return out
+
+    def build(self, records, draws=None, with_labels=True):
+        """records: dicts with REFINE_KEYS (points (n,>=3) float32 rect camera coordinates; box3d (8,3), heading, size (l,w,h)
+        of the label box; pred_box3d (8,3), pred_angle, pred_size of the first-stage prediction; type).  Returns the batch
+        dict on the device (+ 'lens' (B,4) int32: the per-sample window counts before padding)."""
+        if self.device.type != "cuda":
+            raise RuntimeError("frustum_convnet_amd: input construction is a HIP kernel (MI355X only); no CPU fallback")
+        B, N = len(records), self.npoints
+        counts = [len(r["points"]) for r in records]
+        if draws is None:
+            draws = draw_refine(counts, N, self.random_flip and with_labels, self.random_shift and with_labels)
+        choice, coin, normal = draws
+        stride = int(records[0]["points"].shape[1])
+        raw = np.concatenate([np.ascontiguousarray(r["points"], dtype=np.float32) for r in records], 0)
+        off = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+        f64 = lambda k, shape: np.stack([np.asarray(r[k], dtype=np.float64).reshape(shape) for r in records])
+        psize = f64("pred_size", (3,))
+        # batch maxima of len(np.arange(-w/2, w/2, s)): the padded widths of the outputs
+        Lpad = self._lpad(psize[:, 1])
+        dev = self.device
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev, non_blocking=True)
+        t = {"raw": up(raw), "off": up(off), "choice": up(np.asarray(choice, dtype=np.int32)),
+             "pcorners": up(f64("pred_box3d", (24,))), "pangle": up(f64("pred_angle", ())), "psize": up(psize)}
+        if with_labels:
+            t.update(corners=up(f64("box3d", (24,))), heading=up(f64("heading", ())), size=up(f64("size", (3,))),
+                     coin=up(np.asarray(coin, dtype=np.float64)), normal=up(np.asarray(normal, dtype=np.float64)))
+        out = self._launch(t, B, stride, Lpad, with_labels)
         size_class = [self.classes.index(r["type"]) for r in records]
         if with_labels:
             out["size_class"] = torch.tensor(size_class, dtype=torch.int64).view(B, 1).to(dev, non_blocking=True)
         if self.one_hot:
-            oh = np.zeros((B, len(self.classes)), dtype=np.float32)
-            oh[np.arange(B), size_class] = 1.0
-            out["one_hot"] = up(oh)
+            out["one_hot"] = self._one_hot(size_class)
         if not with_labels:
             # from_rgb_detection path (provider_sample_refine.py:404-419): the 2-D detector's score travels with the sample and
             # becomes the detection score's prior in detect() (train/test_net_det.py:214,279)

@@ -544,6 +544,34 @@ int fcn_prepare_inputs_refine(const fcn_inp_refine_desc *d, const float *raw_pts
                               float *const center_ref[4], int64_t *cls_label, float *box3d_center, float *box3d_heading,
                               float *box3d_size, float *rot_angle, float *ref_center, int32_t *lens, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * The link between the two stages of the cascade: first-stage detections -> the raw points of the refinement stage.  Replaces
+ * the host loop of kitti/prepare_data_refine.py::extract_frustum_data_rgb_detection (:649-773): enlarge every predicted box by
+ * `ratio` (1.2 there), keep the frame's points inside it (scipy.spatial.Delaunay(...).find_simplex), pickle them for
+ * datasets/provider_sample_refine.py.
+ *   frame_pts (sum m_f, pt_stride) float32 rect camera coordinates (columns from 3 on are carried along untouched),
+ *   frame_off (F+1) int64 row offsets, dets (R,8) float32 rows as fcn_decode_detections writes them (ty = box bottom),
+ *   cand_row (D) int32 indices into dets, cand_frame (D) int32 in [0, F).
+ * fcn_refine_select_count writes, per candidate and in fp64 like the pickled records fcn_prepare_inputs_refine takes:
+ *   pred_corners (D,8,3) of the ENLARGED box in the order of compute_box_3d_obj_array (:56-79: centre (tx, ty - h/2, tz),
+ *   roty(ry)), pred_angle (D) = ry, pred_size (D,3) = l,w,h * ratio, and cnt (D) int32 = the number of frame points inside.
+ * fcn_refine_select_fill takes out_off (D+1) int64 -- the caller's cumulative sum of cnt -- and writes out_pts
+ * (out_off[D], pt_stride): for candidate d the selected rows of its frame at out_off[d].., in ascending frame order, as bit-exact
+ * copies of all pt_stride floats (rows past out_off[d+1] are dropped, never stored).
+ * Inside: |x'| <= l/2, |dy| <= h/2, |z'| <= w/2 in the enlarged box's frame ((x', z') = p - centre rotated back by ry), evaluated in
+ * fp64 from the fp32 inputs, the same predicate in both calls; a point with a non-finite coordinate is never inside.  (The
+ * reference's Delaunay test has a tolerance at the faces; this box is closed and exact.)
+ * D == 0 or F == 0: nothing to select, returns 0 (cnt is zeroed when F == 0).  A candidate whose row or frame is out of range is
+ * never dereferenced: its cnt is 0, nothing else of it is written, the other candidates are processed and the call returns
+ * FCN_E_BADARG.  To report that, both calls read the two candidate lists back first (a stream synchronisation: not capturable
+ * into a hipGraph). */
+int fcn_refine_select_count(const float *frame_pts, const int64_t *frame_off, int F, int pt_stride, const float *dets, int R,
+                            const int32_t *cand_row, const int32_t *cand_frame, int D, double ratio, double *pred_corners,
+                            double *pred_angle, double *pred_size, int32_t *cnt, void *stream);
+int fcn_refine_select_fill(const float *frame_pts, const int64_t *frame_off, int F, int pt_stride, const float *dets, int R,
+                           const int32_t *cand_row, const int32_t *cand_frame, int D, double ratio, const int64_t *out_off,
+                           float *out_pts, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
