@@ -6,6 +6,7 @@
     from frustum_convnet_amd.train_state import FlatTrainState       # flat parameters / gradients / Adam moments
     from frustum_convnet_amd.inputs import InputBuilder              # batch construction on the device
     from frustum_convnet_amd.cascade import TwoStageDetector         # first-stage boxes -> refine inputs -> second stage
+    from frustum_convnet_amd.frustum import frustum_candidates, image_fov_points   # LiDAR frames + 2-D boxes -> frustum points
 
 Nothing here imports torch or loads libfcn_hip.so eagerly: `_native.lib()` does on first use and raises ImportError
 when the library has not been built (`python -m frustum_convnet_amd.build`); there is no CPU fallback.

@@ -62,10 +62,44 @@ def refine_candidates(frame_points, frame_off, dets, cand_row, cand_frame, ratio
 
 class TwoStageDetector:
     """stage1, stage2: two PointNetDet models in eval mode, each built by the caller under its own configuration (cfg is
-    global: build one, then the other); refine_builder: the RefineInputBuilder of the second stage's configuration."""
+    global: build one, then the other); refine_builder: the RefineInputBuilder of the second stage's configuration;
+    input_builder: the InputBuilder of the first stage's configuration (detect_frames alone needs it)."""
 
-    def __init__(self, stage1, stage2, refine_builder):
-        self.stage1, self.stage2, self.refine_builder = stage1, stage2, refine_builder
+    def __init__(self, stage1, stage2, refine_builder, input_builder=None):
+        self.stage1, self.stage2, self.refine_builder, self.input_builder = stage1, stage2, refine_builder, input_builder
+
+    def detect_frames(self, frame_points_velo, frame_off, calib, img_size, boxes2d, box_frame, types, prob, method, thresh,
+                      unit_group=None, num_groups=None, top_k=300, ratio=1.2, draws=None, refine_draws=None,
+                      clip_distance=2.0, clip_boxes=True, img_height_threshold=5, lidar_point_threshold=1):
+        """From LiDAR frames and a 2-D detector's boxes to second-stage detections: frame_points_velo / frame_off, calib,
+        img_size, boxes2d (D,4), box_frame (D), clip_distance, clip_boxes as frustum.frustum_candidates takes them; types (D) /
+        prob (D): class name and score of each box; unit_group (D) / num_groups: the (frame, class) group of each BOX (default:
+        every surviving box its own); draws / refine_draws: the resample indices of the first / second stage's builder.
+        Steps: frustum_candidates -> input_builder.build_device (drops boxes too small or without points: 'kept') ->
+        image_fov_points -> detect(...) with the kept boxes' frames, types and groups.
+        Returns detect()'s dict + kept (B,) int64 (host): the box each first-stage frustum came from.  With no surviving box
+        every other entry is None (stage1_row is empty)."""
+        from . import frustum
+        if self.input_builder is None:
+            raise ValueError("TwoStageDetector.detect_frames needs the first stage's InputBuilder (input_builder=...)")
+        sel = frustum.frustum_candidates(frame_points_velo, frame_off, calib, img_size, boxes2d, box_frame, clip_distance, clip_boxes)
+        batch = self.input_builder.build_device(sel, calib["P"], types, prob, draws=draws,
+                                                img_height_threshold=img_height_threshold,
+                                                lidar_point_threshold=lidar_point_threshold)
+        kept = batch.pop("kept")
+        if len(kept) == 0:
+            return {"dets": None, "valid": None, "keep": None, "cnt": None, "stage1_row": np.zeros((0,), dtype=np.int64),
+                    "stage1": None, "kept": kept}
+        fov_pts, fov_off = frustum.image_fov_points(frame_points_velo, frame_off, calib, img_size, clip_distance)
+        frame = torch.as_tensor(box_frame).cpu().numpy().reshape(-1).astype(np.int64)[kept]
+        ug = None if unit_group is None else torch.as_tensor(unit_group).cpu().numpy().reshape(-1)[kept]
+        if ug is not None and num_groups is None:
+            num_groups = int(ug.max()) + 1
+        res = self.detect(batch, fov_pts, fov_off, frame, [types[i] for i in kept], method, thresh,
+                          unit_group=None if ug is None else torch.from_numpy(ug.astype(np.int32)), num_groups=num_groups,
+                          top_k=top_k, ratio=ratio, draws=refine_draws)
+        res["kept"] = kept
+        return res
 
     def detect(self, data_dicts, frame_points, frame_off, frustum_frame, types, method, thresh, unit_group=None,
                num_groups=None, top_k=300, ratio=1.2, draws=None):

@@ -53,28 +53,36 @@ __global__ __launch_bounds__(INP_T) void prepare_inputs_kernel(InpArgs a)
     // ---- per-frustum scalars (every thread computes the same values)
     const double rot = M_PI / 2.0 + a.fangle[b];
     const double c = cos(rot), s = sin(rot);
-    const double *cr = a.corners + (int64_t)b * 24;
-    const double c0x = (cr[0] + cr[18]) / 2.0, c0y = (cr[1] + cr[19]) / 2.0, c0z = (cr[2] + cr[20]) / 2.0;
-    double cx = c0x * c + c0z * (-s), cy = c0y, cz = c0x * s + c0z * c;     // (cy: the height shift below moves it)
-    double ang = a.heading[b] - rot;
-    const bool flip = a.d.random_flip && a.coin[b] > 0.5;
-    if (flip) { cx = -cx; ang = M_PI - ang; }
-    const double sl = a.size[3 * b], sw = a.size[3 * b + 1], sh = a.size[3 * b + 2];
+    // corners == nullptr: inference records (fcn_prepare_inputs_infer) -- no label box, so no flip, no shift and no label outputs
+    const bool train = a.corners != nullptr;
+    double cx = 0.0, cy = 0.0, cz = 0.0, ang = 0.0, sl = 0.0, sw = 0.0, sh = 0.0;
+    const bool flip = train && a.d.random_flip && a.coin[b] > 0.5;
+    if (train) {
+        const double *cr = a.corners + (int64_t)b * 24;
+        const double c0x = (cr[0] + cr[18]) / 2.0, c0y = (cr[1] + cr[19]) / 2.0, c0z = (cr[2] + cr[20]) / 2.0;
+        cx = c0x * c + c0z * (-s); cy = c0y; cz = c0x * s + c0z * c;        // (cy: the height shift below moves it)
+        ang = a.heading[b] - rot;
+        if (flip) { cx = -cx; ang = M_PI - ang; }
+        sl = a.size[3 * b]; sw = a.size[3 * b + 1]; sh = a.size[3 * b + 2];
+    }
+    const bool do_shift = train && a.d.random_shift;
     double shift = 0.0;
-    if (a.d.random_shift) {
+    if (do_shift) {
         const double dist = sqrt(sl * sl + sw * sw);
         shift = fmin(fmax(a.normal[b] * dist * 0.2, -0.5 * dist), 0.5 * dist);
         shift = fmin(fmax(shift + cz, 0.0), a.d.max_depth) - cz;
         cz += shift;
     }
     // provider_sample_sunrgbd.py:228-230: height_shift = np.random.random() * 0.4 - 0.2 on the points' y and the box centre
-    const bool has_h = a.d.random_shift && a.hshift != nullptr;
+    const bool has_h = do_shift && a.hshift != nullptr;
     const double hsh = has_h ? a.hshift[b] * 0.4 - 0.2 : 0.0;
     if (has_h) cy += hsh;
     if (tid == 0) {
-        a.center[3 * b] = (float)cx; a.center[3 * b + 1] = (float)cy; a.center[3 * b + 2] = (float)cz;
-        a.head[b] = (float)ang;
-        a.osize[3 * b] = (float)sl; a.osize[3 * b + 1] = (float)sw; a.osize[3 * b + 2] = (float)sh;
+        if (train) {
+            a.center[3 * b] = (float)cx; a.center[3 * b + 1] = (float)cy; a.center[3 * b + 2] = (float)cz;
+            a.head[b] = (float)ang;
+            a.osize[3 * b] = (float)sl; a.osize[3 * b + 1] = (float)sw; a.osize[3 * b + 2] = (float)sh;
+        }
         a.rot[b] = (float)rot;
     }
     // ---- points
@@ -87,7 +95,7 @@ __global__ __launch_bounds__(INP_T) void prepare_inputs_kernel(InpArgs a)
         float xr = (float)(x * c + z * (-s));              // the reference stores the rotated record back as float32
         float zr = (float)(x * s + z * c);
         if (flip) xr = -xr;
-        if (a.d.random_shift) zr = (float)((double)zr + shift);
+        if (do_shift) zr = (float)((double)zr + shift);
         float yr = p[1];
         if (has_h) yr = (float)((double)yr + hsh);         // float32 record += float64 scalar
         float *o = a.pc + (int64_t)b * 3 * N;
@@ -187,6 +195,31 @@ extern "C" int fcn_prepare_inputs(const fcn_inp_desc *d, const float *raw_pts, c
     a.K = nullptr; a.Rtilt = nullptr; a.hshift = nullptr;
     a.pc = point_cloud;
     a.cls = cls_label; a.center = box3d_center; a.head = box3d_heading; a.osize = box3d_size; a.rot = rot_angle; a.seg = seg_label;
+    hipLaunchKernelGGL(prepare_inputs_kernel, dim3(d->B), dim3(INP_T), 0, (hipStream_t)stream, a);
+    FCN_CHECK_LAUNCH();
+    return 0;
+}
+
+// Inference records of the first stage (datasets/provider_sample.py:184-195, from_rgb_detection): no label box in, no labels out,
+// no augmentation -- point_cloud, center_ref[4] and rot_angle alone.  The same kernel with corners == nullptr.
+extern "C" int fcn_prepare_inputs_infer(const fcn_inp_desc *d, const float *raw_pts, const int64_t *pt_off, const int32_t *choice,
+                                        const double *frustum_angle, const double *box2d, const double *P, float *point_cloud,
+                                        float *const center_ref[4], float *rot_angle, void *stream)
+{
+    if (!d || !raw_pts || !pt_off || !choice || !frustum_angle || !box2d || !P || !point_cloud || !center_ref || !rot_angle)
+        return FCN_E_BADARG;
+    if (d->B <= 0 || d->N <= 0 || d->pt_stride < 3 || d->random_flip || d->random_shift) return FCN_E_BADARG;
+    for (int s = 0; s < 4; ++s)
+        if (d->L[s] <= 0 || !(d->stride[s] > 0.0) || !center_ref[s]) return FCN_E_BADARG;
+    InpArgs a;
+    a.d.B = d->B; a.d.N = d->N; a.d.pt_stride = d->pt_stride; a.d.nsc = 4; a.d.max_depth = d->max_depth;
+    a.d.random_flip = 0; a.d.random_shift = 0;
+    for (int s = 0; s < 5; ++s) { a.d.L[s] = s < 4 ? d->L[s] : 0; a.d.stride[s] = s < 4 ? d->stride[s] : 1.0; a.ref[s] = s < 4 ? center_ref[s] : nullptr; }
+    a.raw = raw_pts; a.off = pt_off; a.raw_seg = nullptr; a.choice = choice; a.fangle = frustum_angle;
+    a.box2d = box2d; a.P = P; a.corners = nullptr; a.heading = nullptr; a.size = nullptr; a.coin = nullptr; a.normal = nullptr;
+    a.K = nullptr; a.Rtilt = nullptr; a.hshift = nullptr;
+    a.pc = point_cloud;
+    a.cls = nullptr; a.center = nullptr; a.head = nullptr; a.osize = nullptr; a.rot = rot_angle; a.seg = nullptr;
     hipLaunchKernelGGL(prepare_inputs_kernel, dim3(d->B), dim3(INP_T), 0, (hipStream_t)stream, a);
     FCN_CHECK_LAUNCH();
     return 0;
@@ -390,3 +423,7 @@ extern "C" int fcn_prepare_inputs_refine(const fcn_inp_refine_desc *d, const flo
 // ------------------------------------------------------------------------------------------------
 // First-stage detections -> the raw points of the refinement stage (fcn_refine_select_count / _fill): csrc/refine_select.h
 #include "refine_select.h"
+
+// ------------------------------------------------------------------------------------------------
+// LiDAR frames + calibration + 2-D boxes -> the raw points of the first stage (fcn_frustum_select_count / _fill): csrc/frustum_select.h
+#include "frustum_select.h"

@@ -125,6 +125,60 @@ class InputBuilder:
             out["one_hot"] = t["one_hot"]
         return out
 
+    def build_device(self, sel, P, types, prob, draws=None, img_height_threshold=5, lidar_point_threshold=1):
+        """The first stage's inference batch (the reference's from_rgb_detection dict, provider_sample.py:184-195: point_cloud,
+        rot_angle, rgb_prob, center_ref1..4, one_hot) straight from the device tensors of frustum.frustum_candidates: no point
+        leaves the device.  sel: its dict; P (F,3,4): the frames' projection matrices (calib["P"]), gathered per box through
+        sel["box_frame"]; types / prob: the class name and the 2-D detector's score of each of the D boxes; draws: (choice (B,N)
+        int32, ...) for the B surviving boxes, or None to draw like draw() from their counts (no flip, no shift: inference).
+        A box is dropped when ymax - ymin < img_height_threshold, xmax - xmin < 1 or count < lidar_point_threshold
+        (prepare_data.py:546-548; a box without a point cannot be resampled and is dropped in any case); 'kept' (B,) int64 (host) lists the survivors' box indices.  The host reads the D boxes here.
+        With no survivor the dict holds 'kept' alone."""
+        if self.device.type != "cuda":
+            raise RuntimeError("frustum_convnet_amd: input construction is a HIP kernel (MI355X only); no CPU fallback")
+        counts = np.asarray(sel["counts"], dtype=np.int64)
+        D, N = len(counts), self.npoints
+        if len(types) != D or len(prob) != D:
+            raise ValueError("build_device: %d boxes, %d types, %d prob" % (D, len(types), len(prob)))
+        box = sel["box2d"].cpu().numpy().reshape(D, 4)                        # D boxes: the skip rules
+        skip = (box[:, 3] - box[:, 1] < img_height_threshold) | (box[:, 2] - box[:, 0] < 1) | (counts < lidar_point_threshold)
+        kept = np.nonzero(~skip & (counts > 0))[0]
+        B = len(kept)
+        if B == 0:
+            return {"kept": kept}
+        if draws is None:
+            draws = draw(counts[kept], N, False, False)
+        dev = self.device
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev, non_blocking=True)
+        idx = up(kept)
+        pick = lambda x: x.index_select(0, idx).contiguous()
+        Pd = torch.as_tensor(P).to(device=dev, dtype=torch.float64).reshape(-1, 12)
+        t = {"raw": sel["points"], "choice": up(np.asarray(draws[0], dtype=np.int32)),
+             "off": pick(sel["off"]),                                         # the kernel reads a sample's first row only
+             "fangle": pick(sel["frustum_angle"]), "box2d": pick(sel["box2d"]),
+             "P": Pd.index_select(0, pick(sel["box_frame"]).to(torch.int64)).contiguous()}
+        f32 = dict(dtype=torch.float32, device=dev)
+        out = {"point_cloud": torch.empty((B, 3, N), **f32), "rot_angle": torch.empty((B, 1), **f32)}
+        for s in range(4):
+            out["center_ref%d" % (s + 1)] = torch.empty((B, 3, self.L[s]), **f32)
+        desc = InpDesc(B, N, int(sel["points"].shape[1]), (ctypes.c_int32 * 4)(*self.L), (ctypes.c_double * 4)(*self.strides),
+                       self.max_depth, 0, 0)
+        refs = (ctypes.c_void_p * 4)(*[out["center_ref%d" % (s + 1)].data_ptr() for s in range(4)])
+        p = lambda x: x.data_ptr()
+        with torch.cuda.device(dev):
+            _native.check(_native.lib().fcn_prepare_inputs_infer(
+                ctypes.byref(desc), p(t["raw"]), p(t["off"]), p(t["choice"]), p(t["fangle"]), p(t["box2d"]), p(t["P"]),
+                p(out["point_cloud"]), refs, p(out["rot_angle"]), _native.current_stream(dev)), "fcn_prepare_inputs_infer")
+        for v in t.values():
+            v.record_stream(torch.cuda.current_stream(dev))
+        out["rgb_prob"] = up(np.asarray(prob, dtype=np.float32)[kept].reshape(B, 1))
+        if self.one_hot:
+            oh = np.zeros((B, len(self.classes)), dtype=np.float32)
+            oh[np.arange(B), [self.classes.index(types[i]) for i in kept]] = 1.0
+            out["one_hot"] = up(oh)
+        out["kept"] = kept
+        return out
+
     def algorithmic_bytes(self, B, with_seg=True, pt_stride=4):
         """HBM bytes one launch has to move (the roofline's numerator): per frustum N gathered raw points + their draw indices
         (+ seg labels) in, point cloud + window centres + labels (+ seg) out; the per-frustum scalars (~400 B) ignored."""

@@ -504,6 +504,12 @@ int fcn_prepare_inputs(const fcn_inp_desc *d, const float *raw_pts, const int64_
                        int64_t *cls_label, float *box3d_center, float *box3d_heading, float *box3d_size,
                        float *rot_angle, int64_t *seg_label, void *stream);
 
+/* The same launch for inference records (datasets/provider_sample.py:184-195, from_rgb_detection): no label box in, no label
+ * outputs, no augmentation (d->random_flip / random_shift must be 0).  Writes point_cloud, center_ref[4] and rot_angle. */
+int fcn_prepare_inputs_infer(const fcn_inp_desc *d, const float *raw_pts, const int64_t *pt_off, const int32_t *choice,
+                             const double *frustum_angle, const double *box2d, const double *P, float *point_cloud,
+                             float *const center_ref[4], float *rot_angle, void *stream);
+
 /* SUN-RGBD variant (cfgs/det_sample_sunrgbd.yaml; datasets/provider_sample_sunrgbd.py::ProviderDataset.__getitem__ :116-263,
  * generate_ref :283-326, project_image_to_upright_camera :28-59): five strides; the window centres go through the camera
  * matrix K (B,3,3) and the tilt rotation Rtilt (B,3,3) -- camera (x,y,z) -> (x,z,-y) -> Rtilt . -> (X,-Z,Y) -- instead of
@@ -571,6 +577,41 @@ int fcn_refine_select_count(const float *frame_pts, const int64_t *frame_off, in
 int fcn_refine_select_fill(const float *frame_pts, const int64_t *frame_off, int F, int pt_stride, const float *dets, int R,
                            const int32_t *cand_row, const int32_t *cand_frame, int D, double ratio, const int64_t *out_off,
                            float *out_pts, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * The front of the pipeline: LiDAR frames in VELODYNE coordinates + per-frame calibration + 2-D detection boxes -> the raw
+ * frustum points of the first stage in rect camera coordinates.  Replaces the host loop of
+ * kitti/prepare_data.py::extract_frustum_data_rgb_detection (:462-568; kitti_util.Calibration.project_velo_to_rect /
+ * project_rect_to_image / project_image_to_rect, draw_util.get_lidar_in_image_fov).
+ *   frame_pts (sum m_f, pt_stride) float32 velodyne x, y, z, then columns that travel untouched (3 = intensity),
+ *   frame_off (F+1) int64 row offsets, P (F,3,4), V2C (F,3,4), R0 (F,3,3), img_wh (F,2) = width, height: fp64,
+ *   boxes (D,4) fp64 xmin ymin xmax ymax, box_frame (D) int32 in [0, F).
+ * The grid is (S, D): workgroup (s, d) scans rows [s * seg, min((s + 1) * seg, m)) of box d's frame, seg =
+ * fcn_frustum_select_seg() (a compile-time constant, a multiple of 256); S >= ceil(max m_f / seg), D <= 65535.
+ * fcn_frustum_select_count writes seg_cnt (D,S) int32 (0 for segments beyond the frame) and, per box, box2d (D,4) -- the box
+ * actually used: with clip_boxes != 0 x is clipped to [0, W-1] and y to [0, H-1] first (:523-524) -- and frustum_angle (D) =
+ * -atan2(20, ((cu - P[0,2]) * 20) / P[0,0] + P[0,3] / (-P[0,0])), cu = (xmin + xmax) / 2 of that box (:537-543).
+ * fcn_frustum_select_fill takes seg_off (D*S+1) int64 -- the caller's ONE cumulative sum over the flattened counts; entry d*S is
+ * box d's offset -- and writes out_pts (seg_off[D*S], pt_stride): the selected rows in ascending frame order as (float) rect x,
+ * y, z followed by bit-exact copies of columns 3..pt_stride-1.  A row whose position falls outside its workgroup's slice
+ * [seg_off[i], seg_off[i+1]) is dropped, never stored.
+ * Selected (one predicate for both calls, fp64 from the fp32 row, every sum left to right): ref = V2C . (x,y,z,1), rect = R0 . ref,
+ * img = P . (rect,1), u = img_0 / img_2, v = img_1 / img_2; xmin <= u < xmax, ymin <= v < ymax, 0 <= u < W, 0 <= v < H and
+ * (double)x > clip_distance (the velodyne x; get_lidar_in_image_fov's default is 2.0).  A row with a non-finite x, y or z is never
+ * selected; img_2 has no guard (the reference has none).
+ * D == 0: returns 0, touches nothing.  F == 0: returns 0 (seg_cnt is zeroed).  Both calls read box_frame and frame_off back first (a
+ * stream synchronisation: NOT capturable into a hipGraph; the caller reads the counts between the two anyway): a box whose frame is
+ * out of range is never dereferenced -- its counts are 0, nothing else of it is written, the other boxes are processed and the call
+ * returns FCN_E_BADARG; a frame longer than S * seg rows is FCN_E_BADARG with no launch. */
+int fcn_frustum_select_seg(void);
+int fcn_frustum_select_count(const float *frame_pts, const int64_t *frame_off, int F, int pt_stride, const double *P,
+                             const double *V2C, const double *R0, const double *img_wh, const double *boxes,
+                             const int32_t *box_frame, int D, int S, int clip_boxes, double clip_distance, double *box2d,
+                             double *frustum_angle, int32_t *seg_cnt, void *stream);
+int fcn_frustum_select_fill(const float *frame_pts, const int64_t *frame_off, int F, int pt_stride, const double *P,
+                            const double *V2C, const double *R0, const double *img_wh, const double *boxes,
+                            const int32_t *box_frame, int D, int S, int clip_boxes, double clip_distance, const int64_t *seg_off,
+                            float *out_pts, void *stream);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,490 @@
+"""-m gpu: frustum extraction on the device -- fcn_frustum_select_count / _fill (csrc/frustum_select.h) through the C-ABI,
+frustum.frustum_candidates / image_fov_points, InputBuilder.build_device against build() on host records, and
+TwoStageDetector.detect_frames against the hand-composed sequence of the same calls.  The referee is the fp64 numpy restatement of
+tests/frustum_ref.py (pinned to the reference by tests/test_frustum_referee.py).  Every shape derives from
+fcn_frustum_select_seg().  tests/test_emu_frustum.py runs the same functions on the host emulation of the kernels."""
+import functools
+import os
+
+import numpy as np
+import pytest
+import torch
+
+import frustum_ref
+
+pytestmark = pytest.mark.gpu
+BADARG = 10001                     # FCN_E_BADARG
+NAN_PAYLOAD = 0x7fc12345           # a quiet NaN with a payload: a copy through float arithmetic could lose it
+MARGIN = 1e-6                      # px: the inputs keep this distance from every edge (as the golden fixture does)
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "frustum_select.npz")
+
+
+@functools.lru_cache(maxsize=None)
+def _golden():
+    return dict(np.load(GOLDEN))
+
+
+def _seg():
+    from frustum_convnet_amd import _native
+    return int(_native.lib().fcn_frustum_select_seg())
+
+
+def _lengths(seg):
+    return (0, 1, 63, 64, 65, 255, seg - 1, seg, seg + 1, 2 * seg + 100)
+
+
+def _calib(F):
+    """Frame f takes calibration f % 2 of the golden fixture (KITTI-like; the second a perturbed copy) and its image size."""
+    g = _golden()
+    i = np.arange(F) % 2
+    return g["P"][i].copy(), g["V2C"][i].copy(), g["R0"][i].copy(), g["img_wh"][i].copy()
+
+
+def _back_project(rng, n, P, V2C, R0, W, H, inside):
+    """n float32 velodyne points from random pixels at random depths: within the image when `inside` (3 px from its
+    border: the pinhole inverse below ignores the third row of P, which moves a pixel by less than that), else up to 60 px around."""
+    pad = -3.0 if inside else 60.0
+    u, v, z = rng.uniform(-pad, W + pad, n), rng.uniform(-pad, H + pad, n), rng.uniform(3.0, 60.0, n)
+    x = ((u - P[0, 2]) * z) / P[0, 0] + P[0, 3] / (-P[0, 0])
+    y = ((v - P[1, 2]) * z) / P[1, 1] + P[1, 3] / (-P[1, 1])
+    ref = np.linalg.solve(R0, np.stack([x, y, z]))
+    return np.linalg.solve(V2C[:, :3], ref - V2C[:, 3:4]).T.astype(np.float32)
+
+
+def _frame_boxes(f, W, H):
+    """Three boxes per frame: more than the whole image (all-selected where every point is in the image), one inside, and in turn
+    one that straddles the border, one outside (none-selected), one degenerate after clipping (xmax <= xmin)."""
+    third = [[-60.5, 120.0, 310.25, H + 80.0], [W + 200.0, 50.0, W + 300.0, 150.0], [W + 10.0, 40.0, W + 5.0, 300.0],
+             [900.0, -70.0, W + 40.0, 210.5]][f % 4]
+    return [[-50.0, -50.0, W + 50.0, H + 50.0], [300.25, 100.5, 700.75, 300.0], third]
+
+
+@functools.lru_cache(maxsize=None)
+def _scene(stride):
+    """F = 10 frames of the lengths the kernels' paths turn on, D = 30 boxes; points keep MARGIN from every edge under both clip
+    settings.  Returns the inputs and the referee's answers for clip_boxes on and off."""
+    seg = _seg()
+    lengths = _lengths(seg)
+    F = len(lengths)
+    rng = np.random.RandomState(100 + stride)
+    P, V2C, R0, wh = _calib(F)
+    boxes = np.asarray([b for f in range(F) for b in _frame_boxes(f, *wh[f])], dtype=np.float64)
+    bframe = np.repeat(np.arange(F), 3).astype(np.int32)
+    frames = []
+    for f, n in enumerate(lengths):
+        W, H = wh[f]
+        xyz = _back_project(rng, n, P[f], V2C[f], R0[f], W, H, inside=n <= 255)
+        rects = [frustum_ref.clip_box(b, W, H, c) for b in boxes[bframe == f] for c in (True, False)]
+        for _ in range(100):
+            _, u, v = frustum_ref.project(xyz, P[f], V2C[f], R0[f])
+            close = np.zeros(n, dtype=bool)
+            for r in rects:
+                close |= frustum_ref.edge_distance(u, v, r, W, H) < MARGIN
+            if not close.any():
+                break
+            xyz[close] = _back_project(rng, int(close.sum()), P[f], V2C[f], R0[f], W, H, inside=n <= 255)
+        else:
+            raise RuntimeError("re-draw did not terminate")
+        frames.append(np.concatenate([xyz, rng.uniform(0, 1, (n, stride - 3)).astype(np.float32)], 1))
+    pts = np.concatenate(frames, 0)
+    off = np.concatenate([[0], np.cumsum(lengths)]).astype(np.int64)
+    # in the longest frame: rows that must never be selected whatever they project to, and a payload in the intensity column
+    big = int(off[-2])
+    pts[big + seg + 5, 0], pts[big + 70, 1], pts[big + 2 * seg + 3, 2] = np.nan, np.inf, -np.inf
+    if stride > 3:
+        _, u, v = frustum_ref.project(pts[big:, :3], P[F - 1], V2C[F - 1], R0[F - 1])
+        hit = np.nonzero(frustum_ref.box_mask(u, v, boxes[-2]) & (pts[big:, 0] > 2.0))[0]
+        pts[big + hit[len(hit) // 2]:big + hit[len(hit) // 2] + 1, 3].view(np.uint32)[0] = NAN_PAYLOAD
+    ref = {c: frustum_ref.select(pts, off, P, V2C, R0, wh, boxes, bframe, clip_boxes=c) for c in (True, False)}
+    for c in (True, False):
+        r = ref[c]
+        assert min(e.min() for e in r["edge"] if len(e)) >= MARGIN
+        cnt = r["counts"].reshape(F, 3)
+        assert (cnt[1:6, 0] == np.asarray(lengths[1:6])).all()                     # all-selected
+        assert cnt[1::4, 2].sum() == 0 and cnt[2::4, 2].sum() == 0                 # outside / degenerate: none selected
+        per_seg = _seg_counts([r["index"][27]], 3, seg)[0]                        # the longest frame: rows in every segment
+        assert (per_seg[:2] > seg // 2).all() and per_seg[2] > 0 and (per_seg % 64 != 0).any()
+        assert cnt[9, 1] > 0 and cnt[8, 2] > 0 and cnt[7, 2] > 0
+    assert not np.array_equal(ref[True]["box2d"], ref[False]["box2d"])
+    assert not np.array_equal(ref[True]["counts"], ref[False]["counts"])
+    return {"pts": pts, "off": off, "P": P, "V2C": V2C, "R0": R0, "wh": wh, "boxes": boxes, "bframe": bframe, "ref": ref,
+            "S": 3, "seg": seg, "lengths": lengths}
+
+
+def _dev(a):
+    return torch.from_numpy(np.ascontiguousarray(a)).to("cuda")
+
+
+def _p(t):
+    return None if t is None else t.data_ptr()
+
+
+def _tensors(sc, **over):
+    return {k: _dev(over.get(k, sc[k])) for k in ("pts", "off", "P", "V2C", "R0", "wh", "boxes", "bframe")}
+
+
+def _common(t, S, clip, clipd=2.0, ps=None):
+    return [_p(t["pts"]), _p(t["off"]), t["off"].numel() - 1, t["pts"].shape[1] if ps is None else ps, _p(t["P"]), _p(t["V2C"]),
+            _p(t["R0"]), _p(t["wh"]), _p(t["boxes"]), _p(t["bframe"]), t["bframe"].numel(), S, 1 if clip else 0, clipd]
+
+
+def _count(t, S, clip=True, clipd=2.0):
+    """The raw count entry point on device tensors -> rc, outputs (sentinel-filled first)."""
+    from frustum_convnet_amd import _native
+    D = t["bframe"].numel()
+    o = {"box2d": torch.full((D, 4), -7.0, dtype=torch.float64, device="cuda"),
+         "angle": torch.full((D,), -7.0, dtype=torch.float64, device="cuda"),
+         "scnt": torch.full((D, S), -7, dtype=torch.int32, device="cuda")}
+    rc = _native.lib().fcn_frustum_select_count(*_common(t, S, clip, clipd), _p(o["box2d"]), _p(o["angle"]), _p(o["scnt"]),
+                                                _native.current_stream())
+    torch.cuda.synchronize()
+    return rc, o
+
+
+def _fill(t, S, seg_counts, clip=True, clipd=2.0, guard=5):
+    """The raw fill entry point -> rc, out rows (total, stride), the `guard` poisoned rows behind them, seg_off."""
+    from frustum_convnet_amd import _native
+    ps = t["pts"].shape[1]
+    soff = np.concatenate([[0], np.cumsum(np.asarray(seg_counts).reshape(-1))]).astype(np.int64)
+    out = torch.full((int(soff[-1]) + guard, ps), -7.0, dtype=torch.float32, device="cuda")
+    soff_d = _dev(soff)
+    rc = _native.lib().fcn_frustum_select_fill(*_common(t, S, clip, clipd), _p(soff_d), _p(out), _native.current_stream())
+    torch.cuda.synchronize()
+    return rc, out[:int(soff[-1])].cpu().numpy(), out[int(soff[-1]):].cpu().numpy(), soff
+
+
+def _bits(a):
+    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
+
+
+def _seg_counts(index, S, seg):
+    """Referee indices per box -> the (D, S) segment counts."""
+    return np.asarray([[int(((idx // seg) == s).sum()) for s in range(S)] for idx in index], dtype=np.int64)
+
+
+def _check_rows(got, want, what=""):
+    """Passthrough columns bit-exact; every rect coordinate within 1 float32 ulp of the referee's (no case excluded)."""
+    assert got.shape == want.shape, (what, got.shape, want.shape)
+    if got.shape[1] > 3:
+        assert np.array_equal(_bits(got[:, 3:]), _bits(want[:, 3:])), what
+    ulp = np.spacing(np.abs(want[:, :3]).astype(np.float32)).astype(np.float64)
+    err = np.abs(got[:, :3].astype(np.float64) - want[:, :3].astype(np.float64))
+    if err.size:
+        print("%s rect: worst error %.3f ulp over %d coordinates, %d not bit-identical" %
+              (what, float((err / ulp).max()), err.size, int((err > 0).sum())))
+    assert (err <= ulp).all(), what
+
+
+@pytest.mark.parametrize("clip", [True, False])
+@pytest.mark.parametrize("stride", [3, 4, 5])
+def test_select_entry_points_match_the_referee(stride, clip):
+    sc = _scene(stride)
+    ref, S, seg = sc["ref"][clip], sc["S"], sc["seg"]
+    t = _tensors(sc)
+    rc, o = _count(t, S, clip)
+    assert rc == 0
+    scnt = o["scnt"].cpu().numpy()
+    want_sc = _seg_counts(ref["index"], S, seg)
+    print("cnt", scnt.sum(1).tolist(), "referee", ref["counts"].tolist())
+    assert np.array_equal(scnt, want_sc)                                   # per segment; 0 beyond a frame's length
+    assert np.array_equal(o["box2d"].cpu().numpy(), ref["box2d"])
+    aerr = np.abs(o["angle"].cpu().numpy() - ref["frustum_angle"])
+    print("angle worst abs err %.3e" % aerr.max())
+    assert (aerr <= 1e-12).all()
+    rc, rows, guard, soff = _fill(t, S, scnt, clip)
+    assert rc == 0 and (guard == -7.0).all()
+    want = np.concatenate(ref["rows"], 0)
+    _check_rows(rows, want, "stride %d clip %d" % (stride, clip))
+    # selected row INDICES: the passthrough column identifies the row when there is one; the order is the referee's in any case
+    assert np.array_equal(soff[::S], np.concatenate([[0], np.cumsum(ref["counts"])]))
+    if stride > 3:
+        assert (_bits(rows)[:, 3] == NAN_PAYLOAD).sum() >= 1
+    assert np.isfinite(rows[:, :3]).all()
+    rc2, rows2, _, _ = _fill(t, S, scnt, clip)
+    assert rc2 == 0 and np.array_equal(_bits(rows2), _bits(rows))          # identical over two runs
+    # more segments than any frame needs: the surplus ones count 0
+    rc, o5 = _count(t, S + 2, clip)
+    assert rc == 0 and np.array_equal(o5["scnt"].cpu().numpy(), _seg_counts(ref["index"], S + 2, seg))
+
+
+def test_clip_distance_and_non_finite_rows_are_exact():
+    """x == 2.0 is out, nextafter(2.0) is in; NaN / +-inf in x, y or z is never selected; NaN in column 3 does not matter."""
+    P, V2C, R0, wh = _calib(1)
+    nxt = np.nextafter(np.float32(2.0), np.float32(3.0))
+    pts = np.asarray([[2.0, 0.0, -0.2, 0.5], [nxt, 0.0, -0.2, 0.5], [np.nan, 0.0, -0.2, 0.5], [10.0, np.nan, -0.2, 0.5],
+                      [10.0, 0.0, np.nan, 0.5], [np.inf, 0.0, -0.2, 0.5], [10.0, -np.inf, -0.2, 0.5], [10.0, 0.0, np.inf, 0.5],
+                      [10.0, 0.0, -0.2, np.nan], [-np.inf, 0.0, -0.2, 0.5], [10.0, 0.5, -0.2, 0.25]], dtype=np.float32)
+    off = np.asarray([0, len(pts)], dtype=np.int64)
+    boxes, bframe = np.asarray([[0.0, 0.0, wh[0][0], wh[0][1]]]), np.zeros(1, dtype=np.int32)
+    ref = frustum_ref.select(pts, off, P, V2C, R0, wh, boxes, bframe, clip_boxes=False)
+    assert ref["index"][0].tolist() == [1, 8, 10]
+    assert frustum_ref.select(pts, off, P, V2C, R0, wh, boxes, bframe, False, 1.9)["index"][0].tolist() == [0, 1, 8, 10]
+    t = {k: _dev(v) for k, v in dict(pts=pts, off=off, P=P, V2C=V2C, R0=R0, wh=wh, boxes=boxes, bframe=bframe).items()}
+    rc, o = _count(t, 1, False)
+    assert rc == 0 and o["scnt"].cpu().numpy().tolist() == [[3]]
+    rc, rows, guard, _ = _fill(t, 1, [[3]], False)
+    assert rc == 0 and (guard == -7.0).all()
+    assert np.array_equal(_bits(rows[:, 3]), _bits(pts[[1, 8, 10], 3]))     # the NaN intensity travels as it is
+    _check_rows(rows[[0, 2]], ref["rows"][0][[0, 2]], "edge cases")
+    _check_rows(rows[1:2, :3], ref["rows"][0][1:2, :3], "edge cases")
+    rc, o = _count(t, 1, False, 1.9)
+    assert rc == 0 and o["scnt"].cpu().numpy().tolist() == [[4]]
+
+
+def test_select_rows_that_are_not_16_byte_aligned():
+    """pt_stride 4 takes 16-byte accesses only when the buffers allow it: a view that starts 4 bytes into an allocation must give
+    the same rows through the word-by-word path."""
+    sc = _scene(4)
+    S, ref = sc["S"], sc["ref"][True]
+    t = _tensors(sc)
+    rc, o = _count(t, S)
+    rc_f, rows_a, _, _ = _fill(t, S, o["scnt"].cpu().numpy())
+    assert rc == 0 and rc_f == 0
+    flat = torch.zeros(sc["pts"].size + 1, dtype=torch.float32, device="cuda")
+    flat[1:] = t["pts"].reshape(-1)
+    t["pts"] = flat[1:].view(-1, 4)
+    assert t["pts"].data_ptr() % 16 == 4
+    rc, o2 = _count(t, S)
+    assert rc == 0 and torch.equal(o2["scnt"].cpu(), o["scnt"].cpu())
+    rc, rows, guard, _ = _fill(t, S, o2["scnt"].cpu().numpy())
+    assert rc == 0 and np.array_equal(_bits(rows), _bits(rows_a)) and (guard == -7.0).all()
+    assert len(rows) == ref["counts"].sum()
+
+
+def test_select_nothing_to_do_and_bad_arguments():
+    from frustum_convnet_amd import _native
+    sc = _scene(3)
+    S = sc["S"]
+    t = _tensors(sc)
+    L = _native.lib()
+    s = _native.current_stream()
+    # D = 0: empty box lists (and empty outputs: their pointers may be NULL)
+    t0 = dict(t, boxes=_dev(np.zeros((0, 4))), bframe=_dev(np.zeros(0, np.int32)))
+    rc, o = _count(t0, S)
+    assert rc == 0 and o["scnt"].numel() == 0
+    rc, rows, guard, _ = _fill(t0, S, np.zeros((0, S), np.int64))
+    assert rc == 0 and rows.shape == (0, 3) and (guard == -7.0).all()
+    # F = 0: no frame to search -- the counts are zeroed, nothing else is written
+    tf = dict(t, off=_dev(np.zeros(1, np.int64)))
+    rc, o = _count(tf, S)
+    assert rc == 0 and (o["scnt"].cpu().numpy() == 0).all() and (o["box2d"].cpu().numpy() == -7.0).all()
+    # S too small for the longest frame: refused, nothing launched
+    rc, o = _count(t, S - 1)
+    assert rc == BADARG and (o["scnt"].cpu().numpy() == -7).all() and (o["angle"].cpu().numpy() == -7.0).all()
+    rc, rows, guard, _ = _fill(t, S - 1, np.zeros((t["bframe"].numel(), S - 1), np.int64))
+    assert rc == BADARG
+    rc, o = _count(t, S)
+    assert rc == 0
+    good = _common(t, S, True) + [_p(o["box2d"]), _p(o["angle"]), _p(o["scnt"]), s]
+    assert L.fcn_frustum_select_count(*good) == 0
+    torch.cuda.synchronize()
+    for i in (0, 1, 4, 5, 6, 7, 8, 9, 14, 15, 16):                        # NULL pointers: refused before anything is launched
+        bad = list(good)
+        bad[i] = None
+        assert L.fcn_frustum_select_count(*bad) == BADARG, i
+    for i, v in ((3, 2), (11, 0), (11, -1), (10, -1), (2, -1)):           # pt_stride 2, S < 1, negative sizes
+        bad = list(good)
+        bad[i] = v
+        assert L.fcn_frustum_select_count(*bad) == BADARG, (i, v)
+    scnt = o["scnt"].cpu().numpy()
+    soff = _dev(np.concatenate([[0], np.cumsum(scnt.reshape(-1))]).astype(np.int64))
+    out = torch.zeros((int(scnt.sum()), 3), dtype=torch.float32, device="cuda")
+    goodf = good[:14] + [_p(soff), _p(out), s]
+    assert L.fcn_frustum_select_fill(*goodf) == 0
+    torch.cuda.synchronize()
+    for i in (0, 1, 4, 5, 6, 7, 8, 9, 14, 15):
+        bad = list(goodf)
+        bad[i] = None
+        assert L.fcn_frustum_select_fill(*bad) == BADARG, i
+    for i, v in ((3, 2), (11, 0)):
+        bad = list(goodf)
+        bad[i] = v
+        assert L.fcn_frustum_select_fill(*bad) == BADARG, (i, v)
+
+
+@pytest.mark.parametrize("what", ["frame_high", "frame_negative"])
+def test_out_of_range_box_frame_is_reported_and_never_dereferenced(what):
+    from frustum_convnet_amd import frustum, _native
+    sc = _scene(4)
+    S, ref = sc["S"], sc["ref"][True]
+    F = len(sc["lengths"])
+    bframe = sc["bframe"].copy()
+    bad = 28                                                        # a box of the longest frame
+    bframe[bad] = F if what == "frame_high" else -1
+    t = _tensors(sc, bframe=bframe)                                  # exactly sized buffers: nothing beyond them can be read
+    rc, o = _count(t, S)
+    assert rc == BADARG
+    scnt = o["scnt"].cpu().numpy()
+    want = _seg_counts(ref["index"], S, sc["seg"])
+    want[bad] = 0
+    assert np.array_equal(scnt, want)                                # its counts are 0, every other box is processed
+    got_box, got_ang = o["box2d"].cpu().numpy(), o["angle"].cpu().numpy()
+    assert (got_box[bad] == -7.0).all() and got_ang[bad] == -7.0     # nothing else of it is written
+    ok = np.arange(len(bframe)) != bad
+    assert np.array_equal(got_box[ok], ref["box2d"][ok]) and (np.abs(got_ang[ok] - ref["frustum_angle"][ok]) <= 1e-12).all()
+    rc, rows, guard, _ = _fill(t, S, scnt)
+    assert rc == BADARG and (guard == -7.0).all()
+    _check_rows(rows, np.concatenate([r for d, r in enumerate(ref["rows"]) if d != bad], 0), what)
+    with pytest.raises(_native.NativeError):
+        frustum.frustum_candidates(t["pts"], t["off"], {"P": t["P"], "V2C": t["V2C"], "R0": t["R0"]}, t["wh"], t["boxes"], t["bframe"])
+
+
+def test_fill_never_writes_past_a_slice():
+    """seg_off bounds the writes: with offsets that grant one segment fewer rows than it selects, the surplus is dropped; the
+    neighbours' rows and the poisoned rows behind the buffer stay as they were."""
+    sc = _scene(4)
+    S, seg, ref = sc["S"], sc["seg"], sc["ref"][True]
+    t = _tensors(sc)
+    counts = _seg_counts(ref["index"], S, seg)
+    d, s = 27, 1                                                     # the whole-image box of the longest frame, middle segment
+    assert counts[d, s] > 200
+    counts[d, s] -= 100
+    rc, rows, guard, soff = _fill(t, S, counts)
+    assert rc == 0 and (guard == -7.0).all()                         # (bytes behind the last slice: unchanged)
+    assert len(rows) == ref["counts"].sum() - 100                    # (the buffer is the slices and nothing else)
+    for dd in range(len(counts)):
+        for ss in range(S):
+            i = dd * S + ss
+            sel = ref["rows"][dd][(ref["index"][dd] // seg) == ss][:counts[dd, ss]]
+            _check_rows(rows[soff[i]:soff[i + 1]], sel, "")
+
+
+def _cal(t):
+    return {"P": t["P"], "V2C": t["V2C"], "R0": t["R0"]}
+
+
+def test_image_fov_points_equals_the_referees_fov_selection():
+    from frustum_convnet_amd import frustum
+    sc = _scene(4)
+    t = _tensors(sc)
+    pts, off = frustum.image_fov_points(t["pts"], t["off"], _cal(t), t["wh"])
+    want, cnt = [], []
+    for f in range(len(sc["lengths"])):
+        fr = sc["pts"][sc["off"][f]:sc["off"][f + 1]]
+        rect, u, v = frustum_ref.project(fr[:, :3], sc["P"][f], sc["V2C"][f], sc["R0"][f])
+        m = frustum_ref.fov_mask(fr, u, v, sc["wh"][f][0], sc["wh"][f][1])
+        rows = fr[m].copy()
+        rows[:, :3] = rect[m].astype(np.float32)
+        want.append(rows)
+        cnt.append(int(m.sum()))
+    assert np.array_equal(off.cpu().numpy(), np.concatenate([[0], np.cumsum(cnt)])) and off.dtype == torch.int64
+    assert 0 < cnt[-1] < sc["lengths"][-1] and cnt[0] == 0
+    _check_rows(pts.cpu().numpy(), np.concatenate(want, 0), "image fov")
+    # the frame_points / frame_off pair refine_candidates expects
+    assert pts.dtype == torch.float32 and pts.shape[1] == 4 and off.numel() == len(sc["lengths"]) + 1
+
+
+def _input_builder(npoints):
+    from frustum_convnet_amd import inputs
+    from frustum_convnet_amd.config import reset_cfg
+    reset_cfg()
+    return inputs.InputBuilder(npoints, strides=(0.25, 0.5, 1.0, 2.0), max_depth=70.0)
+
+
+def test_build_device_equals_build_on_host_records():
+    """InputBuilder.build_device on the device selection of the golden fixture's frames against build(records) on host records
+    made from the DOWNLOADED selection with the same draws: bit-identical on every shared key; the skip rules drop exactly the
+    boxes the reference drops (height < 5 px, width < 1 px, no point)."""
+    from frustum_convnet_amd import frustum, inputs
+    g = _golden()
+    b = _input_builder(256)
+    cal = {k: _dev(g[k]) for k in ("P", "V2C", "R0")}
+    sel = frustum.frustum_candidates(_dev(g["points"]), _dev(g["off"]), cal, g["img_wh"], g["boxes"], g["box_frame"])
+    D = len(g["boxes"])
+    counts = g["ref_mask"].sum(1)
+    assert np.array_equal(sel["counts"], counts) and sel["counts"].dtype == np.int64
+    assert np.array_equal(sel["cnt"].cpu().numpy(), counts) and sel["cnt"].dtype == torch.int32
+    assert np.array_equal(sel["off"].cpu().numpy(), np.concatenate([[0], np.cumsum(counts)]))
+    assert np.array_equal(sel["box2d"].cpu().numpy(), g["ref_box2d"])
+    assert (np.abs(sel["frustum_angle"].cpu().numpy() - g["ref_angle"]) <= 1e-12).all()
+    pts_h, off_h = sel["points"].cpu().numpy(), sel["off"].cpu().numpy()
+    for d, f in enumerate(g["box_frame"]):                           # against the REFERENCE's recorded rows
+        n = int(g["off"][f + 1] - g["off"][f])
+        m = g["ref_mask"][d, :n]
+        want = np.concatenate([g["ref_rect"][g["off"][f]:g["off"][f + 1]][m], g["points"][g["off"][f]:g["off"][f + 1]][m, 3:]], 1)
+        _check_rows(pts_h[off_h[d]:off_h[d + 1]], want, "box %d" % d)
+    types = ["Car", "Pedestrian", "Cyclist"] * 3
+    prob = np.linspace(0.2, 0.95, D)
+    kept = np.nonzero(~g["ref_skip"])[0]
+    assert 0 < len(kept) < D
+    draws = inputs.draw(counts[kept], 256, False, False, rng=np.random.RandomState(3))
+    assert (counts[kept] < 256).any() and (counts[kept] > 256).any()         # both resample modes
+    got = b.build_device(sel, cal["P"], types, prob, draws=draws)
+    assert np.array_equal(got["kept"], kept) and got["kept"].dtype == np.int64
+    box_h, ang_h = sel["box2d"].cpu().numpy(), sel["frustum_angle"].cpu().numpy()
+    recs = [{"points": pts_h[off_h[d]:off_h[d + 1]], "seg": np.zeros(int(counts[d])), "box2d": box_h[d],
+             "P": g["P"][g["box_frame"][d]], "box3d": np.zeros((8, 3)), "heading": 0.0, "size": np.ones(3),
+             "frustum_angle": float(ang_h[d]), "type": types[d]} for d in kept]
+    want = b.build(recs, draws=draws, with_seg=False)
+    torch.cuda.synchronize()
+    for k in ("point_cloud", "rot_angle", "center_ref1", "center_ref2", "center_ref3", "center_ref4", "one_hot"):
+        assert got[k].dtype == want[k].dtype and got[k].shape == want[k].shape, k
+        assert torch.equal(got[k].cpu(), want[k].cpu()), k
+    assert np.array_equal(got["rgb_prob"].cpu().numpy().ravel(), prob.astype(np.float32)[kept]) and got["rgb_prob"].shape == (len(kept), 1)
+    assert sorted(got.keys()) == sorted(["point_cloud", "rot_angle", "rgb_prob", "center_ref1", "center_ref2", "center_ref3",
+                                         "center_ref4", "one_hot", "kept"])
+    # other thresholds move the skip rules; nobody survives: 'kept' alone
+    got2 = b.build_device(sel, cal["P"], types, prob, img_height_threshold=3, lidar_point_threshold=12)
+    assert got2["kept"].tolist() == [d for d in range(D) if g["ref_box2d"][d, 3] - g["ref_box2d"][d, 1] >= 3 and
+                                     g["ref_box2d"][d, 2] - g["ref_box2d"][d, 0] >= 1 and counts[d] >= 12]
+    assert 4 not in got2["kept"] and 4 not in kept                   # (11 points in a 3.5 px box: each threshold decides it once)
+    assert list(b.build_device(sel, cal["P"], types, prob, lidar_point_threshold=10 ** 6).keys()) == ["kept"]
+
+
+def test_detect_frames_equals_the_hand_composed_sequence():
+    """A car first stage and a refine second stage (N = 512, hash-initialised): TwoStageDetector.detect_frames == frustum_candidates,
+    InputBuilder.build_device, image_fov_points, detect(...) by hand, bit for bit."""
+    from helpers import load_golden
+    from test_gpu_model import _model
+    from frustum_convnet_amd import cascade, frustum, inputs
+    g = _golden()
+    g1, g2 = load_golden("car_b4_n512"), load_golden("refine_b4_n512")
+    m1 = _model(g1).eval()
+    ib = inputs.InputBuilder(int(g1["meta_npoint"]))                 # (cfg holds the first stage's strides here ...)
+    m2 = _model(g2).eval()
+    rb = inputs.RefineInputBuilder(int(g2["meta_npoint"]))           # (... and the refine strides here)
+    # two dense frames in front of the car: every first-stage box finds LiDAR points around it
+    rng = np.random.RandomState(9)
+    lengths = (6000, 5000)
+    xyz = [np.stack([rng.uniform(3, 45, n), rng.uniform(-12, 12, n), rng.uniform(-2.0, 0.5, n), rng.uniform(0, 1, n)], 1) for n in lengths]
+    fpts = _dev(np.concatenate(xyz, 0).astype(np.float32))
+    foff = _dev(np.concatenate([[0], np.cumsum(lengths)]).astype(np.int64))
+    cal = {k: _dev(g[k]) for k in ("P", "V2C", "R0")}
+    wh = g["img_wh"]
+    boxes = np.asarray([[300.0, 150.0, 520.0, 300.0], [700.0, 160.0, 900.0, 280.0], [600.0, 180.0, 700.0, 183.5],
+                        [500.0, 120.0, 760.0, 330.0], [100.0, 150.0, 330.0, 290.0], [640.0, 2.0, 660.0, 9.0]])
+    bframe = np.asarray([0, 0, 0, 1, 1, 1], dtype=np.int32)
+    types = ["Car", "Pedestrian", "Car", "Car", "Cyclist", "Car"]
+    prob = np.asarray([0.9, 0.8, 0.7, 0.6, 0.5, 0.4])
+    group = np.asarray([0, 1, 0, 2, 3, 2], dtype=np.int32)           # (frame, class) groups of the BOXES
+    kw = dict(method="nms", thresh=0.1, top_k=6)
+    # ---- by hand
+    np.random.seed(11)
+    sel = frustum.frustum_candidates(fpts, foff, cal, wh, boxes, bframe)
+    batch = ib.build_device(sel, cal["P"], types, prob)
+    kept = batch.pop("kept")
+    print("points per box", sel["counts"].tolist(), "kept", kept.tolist())
+    assert kept.tolist() == [0, 1, 3, 4]
+    fov_pts, fov_off = frustum.image_fov_points(fpts, foff, cal, wh)
+    two = cascade.TwoStageDetector(m1, m2, rb, input_builder=ib)
+    want = two.detect(batch, fov_pts, fov_off, bframe[kept], [types[i] for i in kept], "nms", 0.1,
+                      unit_group=torch.from_numpy(group[kept]), num_groups=4, top_k=6)
+    # ---- the driver
+    np.random.seed(11)
+    res = two.detect_frames(fpts, foff, cal, wh, boxes, bframe, types, prob, unit_group=group, num_groups=4, **kw)
+    torch.cuda.synchronize()
+    assert np.array_equal(res["kept"], kept)
+    print("second stage units", len(want["stage1_row"]), "detections", None if want["cnt"] is None else int(want["cnt"].sum()))
+    assert want["dets"] is not None and int(want["cnt"].sum()) > 0    # the comparison below is of a real second stage
+    for k in ("dets", "valid", "keep", "cnt"):
+        assert torch.equal(res[k].cpu(), want[k].cpu()), k
+    for a, w in zip(res["stage1"], want["stage1"]):
+        assert torch.equal(a.cpu(), w.cpu())
+    assert np.array_equal(res["stage1_row"], want["stage1_row"])
+    assert torch.isfinite(res["dets"]).all()
+    # without the first stage's builder the driver refuses; two-argument-plus-builder construction is unaffected
+    with pytest.raises(ValueError):
+        cascade.TwoStageDetector(m1, m2, rb).detect_frames(fpts, foff, cal, wh, boxes, bframe, types, prob, **kw)
+    # no box survives: nothing runs
+    none = two.detect_frames(fpts, foff, cal, wh, boxes[[2, 5]], bframe[[2, 5]], ["Car", "Car"], prob[[2, 5]], **kw)
+    assert none["dets"] is None and none["stage1"] is None and len(none["kept"]) == 0 and len(none["stage1_row"]) == 0
