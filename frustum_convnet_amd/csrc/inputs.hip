@@ -427,3 +427,8 @@ extern "C" int fcn_prepare_inputs_refine(const fcn_inp_refine_desc *d, const flo
 // ------------------------------------------------------------------------------------------------
 // LiDAR frames + calibration + 2-D boxes -> the raw points of the first stage (fcn_frustum_select_count / _fill): csrc/frustum_select.h
 #include "frustum_select.h"
+
+// ------------------------------------------------------------------------------------------------
+// The same with one ground-truth 3-D box beside each 2-D box: the first stage's TRAINING records -- points, per-point foreground
+// labels, box corners (fcn_frustum_label_count / _fill): csrc/frustum_label.h
+#include "frustum_label.h"

@@ -1,5 +1,7 @@
 """Frustum extraction on the device: LiDAR frames in velodyne coordinates + calibration + 2-D detection boxes -> the first
-stage's raw frustum points and the refine stage's search set (C-ABI fcn_frustum_select_count / _fill, csrc/frustum_select.h).
+stage's raw frustum points and the refine stage's search set (C-ABI fcn_frustum_select_count / _fill, csrc/frustum_select.h), and,
+with a ground-truth 3-D box beside each 2-D box, the first stage's training records: points, per-point labels, corners
+(fcn_frustum_label_count / _fill, csrc/frustum_label.h; kitti/prepare_data.py::extract_frustum_data :260-391 in the reference).
 
 Reference: kitti/prepare_data.py::extract_frustum_data_rgb_detection (:462-568) projects the whole frame to the image once per
 frame in numpy (kitti_util.Calibration.project_velo_to_rect / project_rect_to_image, draw_util.get_lidar_in_image_fov) and masks
@@ -29,6 +31,33 @@ def _calib(calib, img_size, F, dev):
     return out + [wh.view(F, 2)]
 
 
+def _setup(who, frame_points, frame_off, calib, img_size, boxes2d, box_frame, clip_distance, clip_boxes):
+    """The arguments both pairs of entry points share (fs_in of _native.py) from the Python-level inputs, the tensors that back
+    them, and F, ps, D, S."""
+    _need_cuda(frame_points, who)
+    dev = frame_points.device
+    pts = frame_points.detach().contiguous().float()
+    if pts.dim() != 2 or pts.shape[1] < 3:
+        raise ValueError("%s: frame_points must be (n, >= 3), got %s" % (who, tuple(frame_points.shape)))
+    foff_h = torch.as_tensor(frame_off).detach().cpu().to(torch.int64).contiguous().view(-1)      # F + 1 integers: they decide S
+    foff = foff_h.to(dev, non_blocking=True)
+    F, ps = int(foff_h.numel()) - 1, int(pts.shape[1])
+    P, V2C, R0, wh = _calib(calib, img_size, F, dev)
+    boxes = torch.as_tensor(boxes2d).to(device=dev, dtype=torch.float64).contiguous().view(-1, 4)
+    bframe = torch.as_tensor(box_frame).to(device=dev, dtype=torch.int32).contiguous().view(-1)
+    D = int(bframe.numel())
+    if boxes.shape[0] != D:
+        raise ValueError("%s: %d boxes but %d frames" % (who, boxes.shape[0], D))
+    seg = int(_native.lib().fcn_frustum_select_seg())
+    longest = int((foff_h[1:] - foff_h[:-1]).max()) if F > 0 else 0
+    S = max(1, -(-longest // seg))
+    if pts.shape[0] == 0:
+        pts = torch.zeros((1, ps), dtype=torch.float32, device=dev)        # (an address to hand in: every frame is empty)
+    args = (pts.data_ptr(), foff.data_ptr(), F, ps, P.data_ptr(), V2C.data_ptr(), R0.data_ptr(), wh.data_ptr(), boxes.data_ptr(),
+            bframe.data_ptr(), D, S, 1 if clip_boxes else 0, float(clip_distance))
+    return args, (pts, foff, P, V2C, R0, wh, boxes, bframe), ps, D, S
+
+
 def frustum_candidates(frame_points, frame_off, calib, img_size, boxes2d, box_frame, clip_distance=2.0, clip_boxes=True):
     """frame_points (sum m_f, stride >= 3) float32 VELODYNE x, y, z (+ intensity, ...) of F frames packed behind each other,
     frame_off (F+1) int64 row offsets, calib {"P": (F,3,4), "V2C": (F,3,4), "R0": (F,3,3)} float64, img_size (F,2) as width,
@@ -38,31 +67,13 @@ def frustum_candidates(frame_points, frame_off, calib, img_size, boxes2d, box_fr
     camera x, y, z followed by the untouched columns; off (D+1) int64; box2d (D,4) fp64 the box actually used; frustum_angle
     (D) fp64; cnt (D) int32; box_frame (D) int32 -- on the device -- and counts (D) int64 on the host.  The host reads the D * S
     segment counts once, between the two launches (S = the longest frame in segments of fcn_frustum_select_seg() rows)."""
-    _need_cuda(frame_points, "frustum_candidates")
+    args, held, ps, D, S = _setup("frustum_candidates", frame_points, frame_off, calib, img_size, boxes2d, box_frame,
+                                  clip_distance, clip_boxes)
     dev = frame_points.device
-    pts = frame_points.detach().contiguous().float()
-    if pts.dim() != 2 or pts.shape[1] < 3:
-        raise ValueError("frustum_candidates: frame_points must be (n, >= 3), got %s" % (tuple(frame_points.shape),))
-    foff_h = torch.as_tensor(frame_off).detach().cpu().to(torch.int64).contiguous().view(-1)      # F + 1 integers: they decide S
-    foff = foff_h.to(dev, non_blocking=True)
-    F, ps = int(foff_h.numel()) - 1, int(pts.shape[1])
-    P, V2C, R0, wh = _calib(calib, img_size, F, dev)
-    boxes = torch.as_tensor(boxes2d).to(device=dev, dtype=torch.float64).contiguous().view(-1, 4)
-    bframe = torch.as_tensor(box_frame).to(device=dev, dtype=torch.int32).contiguous().view(-1)
-    D = int(bframe.numel())
-    if boxes.shape[0] != D:
-        raise ValueError("frustum_candidates: %d boxes but %d frames" % (boxes.shape[0], D))
     L = _native.lib()
-    seg = int(L.fcn_frustum_select_seg())
-    longest = int((foff_h[1:] - foff_h[:-1]).max()) if F > 0 else 0
-    S = max(1, -(-longest // seg))
-    if pts.shape[0] == 0:
-        pts = torch.zeros((1, ps), dtype=torch.float32, device=dev)        # (an address to hand in: every frame is empty)
     f64 = dict(dtype=torch.float64, device=dev)
-    out = {"box2d": torch.zeros((D, 4), **f64), "frustum_angle": torch.zeros((D,), **f64), "box_frame": bframe}
+    out = {"box2d": torch.zeros((D, 4), **f64), "frustum_angle": torch.zeros((D,), **f64), "box_frame": held[-1]}
     scnt = torch.zeros((D, S), dtype=torch.int32, device=dev)
-    args = (pts.data_ptr(), foff.data_ptr(), F, ps, P.data_ptr(), V2C.data_ptr(), R0.data_ptr(), wh.data_ptr(), boxes.data_ptr(),
-            bframe.data_ptr(), D, S, 1 if clip_boxes else 0, float(clip_distance))
     with torch.cuda.device(dev):
         _native.check(L.fcn_frustum_select_count(*args, out["box2d"].data_ptr(), out["frustum_angle"].data_ptr(),
                                                  scnt.data_ptr(), _native.current_stream(dev)), "fcn_frustum_select_count")
@@ -88,3 +99,99 @@ def image_fov_points(frame_points, frame_off, calib, img_size, clip_distance=2.0
     boxes = torch.cat([torch.zeros((F, 2), dtype=torch.float64), wh], 1)
     sel = frustum_candidates(frame_points, frame_off, calib, wh, boxes, np.arange(F, dtype=np.int32), clip_distance, False)
     return sel["points"], sel["off"]
+
+
+def perturb_boxes2d(boxes2d, img_wh, shift_ratio=0.1, rng=np.random):
+    """kitti/prepare_data.py::random_shift_box2d (:55-77) for D boxes in order: the centre moves by up to shift_ratio of the width
+    / height, both scale by 1 +- shift_ratio, then x is clipped to [0, W-1] and y to [0, H-1]; an attempt whose clipped box is
+    degenerate is drawn again.  Four rng.random() draws per attempt, in the reference's order, so with the same seed the boxes
+    equal the reference's bit for bit and the generator is left in the reference's state.  boxes2d (D,4) xmin ymin xmax ymax;
+    img_wh (2,) or (D,2) as width, height.  augmentX perturbed copies of a box: repeat its row.  Returns (D,4) float64 (host).
+    ValueError: a box with xmin >= xmax or ymin >= ymax (the reference asserts), and a box that no draw can make valid (it lies
+    beyond the image: the reference would loop for ever)."""
+    boxes = np.asarray(boxes2d, dtype=np.float64).reshape(-1, 4)
+    wh = np.broadcast_to(np.asarray(img_wh, dtype=np.float64).reshape(-1, 2), (len(boxes), 2))
+    r = shift_ratio
+    out = np.empty_like(boxes)
+    for d, (xmin, ymin, xmax, ymax) in enumerate(boxes.tolist()):
+        if not (xmin < xmax and ymin < ymax):
+            raise ValueError("perturb_boxes2d: box %d is degenerate: %r" % (d, (xmin, ymin, xmax, ymax)))
+        W, H = float(wh[d, 0]), float(wh[d, 1])
+        h, w = ymax - ymin, xmax - xmin
+        cx, cy = (xmin + xmax) / 2.0, (ymin + ymax) / 2.0
+        # the furthest any draw reaches: centre shift w * r plus half the largest width w * (1 + r) / 2
+        rx, ry = w * r + w * (1 + r) / 2.0, h * r + h * (1 + r) / 2.0
+        if not (cx - rx < W - 1 and cx + rx > 0 and cy - ry < H - 1 and cy + ry > 0):
+            raise ValueError("perturb_boxes2d: box %d cannot be perturbed into the %g x %g image: %r" % (d, W, H, (xmin, ymin, xmax, ymax)))
+        for _ in range(100000):
+            cx2 = cx + w * r * (rng.random() * 2 - 1)
+            cy2 = cy + h * r * (rng.random() * 2 - 1)
+            h2 = h * (1 + rng.random() * 2 * r - r)
+            w2 = w * (1 + rng.random() * 2 * r - r)
+            new = np.array([cx2 - w2 / 2.0, cy2 - h2 / 2.0, cx2 + w2 / 2.0, cy2 + h2 / 2.0])
+            new[[0, 2]] = np.clip(new[[0, 2]], 0, W - 1)
+            new[[1, 3]] = np.clip(new[[1, 3]], 0, H - 1)
+            if new[0] < new[2] and new[1] < new[3]:
+                break
+        else:
+            raise ValueError("perturb_boxes2d: no valid draw for box %d in 100000 attempts: %r" % (d, (xmin, ymin, xmax, ymax)))
+        out[d] = new
+    return out
+
+
+def frustum_training_candidates(frame_points, frame_off, calib, img_size, boxes2d, box_frame, gt_box3d, gt_box2d=None,
+                                min_box_height=25.0, clip_distance=2.0):
+    """The first stage's TRAINING records from LiDAR frames and label boxes, on the device: what
+    kitti/prepare_data.py::extract_frustum_data (:260-391) pickles.  frame_points ... box_frame as frustum_candidates takes them;
+    boxes2d (D,4): the boxes that select the points -- perturbed (perturb_boxes2d) or plain, used WITHOUT clipping as the
+    reference does; gt_box3d (D,7): tx, ty, tz, l, w, h, ry of the label beside each box (rect camera coordinates, t the bottom
+    centre); gt_box2d (D,4): the unperturbed label boxes the reject rule looks at (default: boxes2d).
+    Box d is dropped when gt_box2d[d,3] - gt_box2d[d,1] < min_box_height or none of its points lies inside its 3-D box (:354);
+    dropped boxes take no room in the packed buffers.
+    Returns a dict over the K kept boxes: points (sum cnt, stride) float32 rect x, y, z + the untouched columns and seg (sum cnt)
+    int64 (1 inside the 3-D box) ; off (K+1) int64; box2d (K,4), frustum_angle (K), box3d (K,8,3) corners, heading (K), size (K,3)
+    fp64; box_frame (K), cnt (K), pos (K) int32 -- on the device -- and kept (K) int64 (the kept boxes' indices), counts (K) int64
+    on the host.  With no survivor the dict holds 'kept' alone.
+    The host reads the D * S selected and positive segment counts once, together, between the two launches; nothing else."""
+    who = "frustum_training_candidates"
+    args, held, ps, D, S = _setup(who, frame_points, frame_off, calib, img_size, boxes2d, box_frame, clip_distance, False)
+    dev = frame_points.device
+    bframe = held[-1]
+    gt = torch.as_tensor(gt_box3d).to(device=dev, dtype=torch.float64).contiguous().view(-1, 7)
+    # the reject rule's boxes live on the host (label files are read there); boxes2d given as a device tensor costs a read of D boxes
+    gt2d = boxes2d if gt_box2d is None else gt_box2d
+    gt2d = (gt2d.detach().cpu().numpy() if isinstance(gt2d, torch.Tensor) else np.asarray(gt2d)).astype(np.float64).reshape(-1, 4)
+    if gt.shape[0] != D or gt2d.shape[0] != D:
+        raise ValueError("%s: %d boxes, %d gt_box3d, %d gt_box2d" % (who, D, gt.shape[0], gt2d.shape[0]))
+    if D == 0:
+        return {"kept": np.zeros(0, dtype=np.int64)}
+    L = _native.lib()
+    f64 = dict(dtype=torch.float64, device=dev)
+    box2d, angle, corners = torch.zeros((D, 4), **f64), torch.zeros((D,), **f64), torch.zeros((D, 8, 3), **f64)
+    both = torch.zeros((2, D, S), dtype=torch.int32, device=dev)            # selected, positive: one read
+    with torch.cuda.device(dev):
+        _native.check(L.fcn_frustum_label_count(*args, gt.data_ptr(), box2d.data_ptr(), angle.data_ptr(), both[0].data_ptr(),
+                                                both[1].data_ptr(), corners.data_ptr(), _native.current_stream(dev)),
+                      "fcn_frustum_label_count")
+        both_h = both.cpu().numpy().astype(np.int64)                        # 2 * D * S integers
+        seg_counts, positives = both_h[0], both_h[1].sum(1)
+        drop = (gt2d[:, 3] - gt2d[:, 1] < min_box_height) | (positives == 0)
+        kept = np.nonzero(~drop)[0].astype(np.int64)
+        if len(kept) == 0:
+            return {"kept": kept}
+        seg_counts[drop] = 0
+        seg_off = np.concatenate([[0], np.cumsum(seg_counts.reshape(-1))]).astype(np.int64)
+        soff = torch.from_numpy(seg_off).to(dev, non_blocking=True)
+        total = int(seg_off[-1])
+        points = torch.empty((total, ps), dtype=torch.float32, device=dev)
+        seg = torch.empty((total,), dtype=torch.int64, device=dev)
+        _native.check(L.fcn_frustum_label_fill(*args, gt.data_ptr(), soff.data_ptr(), points.data_ptr(), seg.data_ptr(),
+                                               _native.current_stream(dev)), "fcn_frustum_label_fill")
+    idx = torch.from_numpy(kept).to(dev, non_blocking=True)
+    pick = lambda x: x.index_select(0, idx).contiguous()
+    # a dropped box has no rows, so a kept box ends where the next kept one starts
+    off = torch.cat([soff[::S][:D].index_select(0, idx), soff[-1:]])
+    return {"points": points, "seg": seg, "off": off, "box2d": pick(box2d), "frustum_angle": pick(angle), "box3d": pick(corners),
+            "heading": pick(gt[:, 6]), "size": pick(gt[:, 3:6]), "box_frame": pick(bframe),
+            "cnt": pick(both[0].sum(1, dtype=torch.int32)), "pos": pick(both[1].sum(1, dtype=torch.int32)),
+            "kept": kept, "counts": seg_counts.sum(1)[kept]}

@@ -179,6 +179,39 @@ class InputBuilder:
         out["kept"] = kept
         return out
 
+    def build_device_train(self, sel, P, types, draws=None, with_seg=True, out=None):
+        """The first stage's TRAINING batch -- the dict of build(), same keys, shapes and dtypes -- straight from the device
+        tensors of frustum.frustum_training_candidates: no point, label or corner leaves the device.  sel: its dict; P (F,3,4):
+        the frames' projection matrices, gathered per box through sel["box_frame"]; types: the class name of each of the D boxes
+        frustum_training_candidates was given (the kept ones are looked up through sel["kept"]); draws: (choice (K,N) int32,
+        coin (K), normal (K)) for the K kept boxes, or None to draw like the reference from their counts; out: launch()'s.
+        ONE launch of fcn_prepare_inputs.  With no kept box the dict holds 'kept' alone."""
+        if self.device.type != "cuda":
+            raise RuntimeError("frustum_convnet_amd: input construction is a HIP kernel (MI355X only); no CPU fallback")
+        kept = np.asarray(sel["kept"], dtype=np.int64)
+        K = len(kept)
+        if K == 0:
+            return {"kept": kept}
+        if draws is None:
+            draws = draw(sel["counts"], self.npoints, self.random_flip, self.random_shift)
+        choice, coin, normal = draws
+        dev = self.device
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev, non_blocking=True)
+        Pd = torch.as_tensor(P).to(device=dev, dtype=torch.float64).reshape(-1, 12)
+        t = {"raw": sel["points"], "off": sel["off"], "seg": sel["seg"] if with_seg else None,
+             "choice": up(np.asarray(choice, dtype=np.int32)), "fangle": sel["frustum_angle"], "box2d": sel["box2d"],
+             "P": Pd.index_select(0, sel["box_frame"].to(torch.int64)).contiguous(), "corners": sel["box3d"].reshape(K, 24),
+             "heading": sel["heading"], "size": sel["size"], "coin": up(np.asarray(coin, dtype=np.float64)),
+             "normal": up(np.asarray(normal, dtype=np.float64))}
+        size_class = [self.classes.index(types[i]) for i in kept]
+        t["size_class"] = torch.tensor(size_class, dtype=torch.int64).view(K, 1).to(dev, non_blocking=True)
+        if self.one_hot:
+            oh = np.zeros((K, len(self.classes)), dtype=np.float32)
+            oh[np.arange(K), size_class] = 1.0
+            t["one_hot"] = up(oh)
+        t["B"], t["pt_stride"] = K, int(sel["points"].shape[1])
+        return self.launch(t, out)
+
     def algorithmic_bytes(self, B, with_seg=True, pt_stride=4):
         """HBM bytes one launch has to move (the roofline's numerator): per frustum N gathered raw points + their draw indices
         (+ seg labels) in, point cloud + window centres + labels (+ seg) out; the per-frustum scalars (~400 B) ignored."""

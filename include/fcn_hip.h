@@ -613,6 +613,38 @@ int fcn_frustum_select_fill(const float *frame_pts, const int64_t *frame_off, in
                             const int32_t *box_frame, int D, int S, int clip_boxes, double clip_distance, const int64_t *seg_off,
                             float *out_pts, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * The same front for TRAINING: one ground-truth 3-D box beside each 2-D box.  Replaces the host loop of
+ * kitti/prepare_data.py::extract_frustum_data (:260-391): the per-point foreground label (extract_pc_in_box3d :31-41, a Delaunay
+ * hull of the corners there, the analytic test below here) and the box corners (kitti_util.compute_box_3d :324-359).  Every
+ * argument of the select pair keeps its meaning; the grid, the segments, the selection predicate and the selected rows are theirs.
+ *   gt_box3d (D,7) fp64 = tx, ty, tz, l, w, h, ry in rect camera coordinates as a KITTI label file has them: t is the centre of
+ *   the box's BOTTOM face, y points down, ry turns about y.
+ * fcn_frustum_label_count writes what fcn_frustum_select_count writes plus seg_pos (D,S) int32 -- the selected rows of the segment
+ * that lie inside the 3-D box -- and corners (D,8,3) fp64 = roty(ry) . (x_k, y_k, z_k) + t with x_k = l/2 l/2 -l/2 -l/2 (twice),
+ * y_k = 0 (four times) then -h, z_k = w/2 -w/2 -w/2 w/2 (twice): compute_box_3d's order.
+ * fcn_frustum_label_fill writes what fcn_frustum_select_fill writes plus out_seg (seg_off[D*S]) int64: 1 for a row inside the box,
+ * else 0, at the row's position in out_pts.  seg_off bounds both stores: a row outside its workgroup's slice is dropped from both,
+ * so a box whose slices are all empty writes nothing (the way to leave a rejected box out of the packed buffers).
+ * Inside (one function for both calls, fp64, every sum left to right) is decided on the row's rect coordinates AFTER their rounding
+ * to float32, the values out_pts holds: c = cos(ry), s = sin(ry), dx = x - tx, dy = y - ty, dz = z - tz, ax = c * dx - s * dz,
+ * az = s * dx + c * dz; inside iff |ax| <= l/2, |az| <= w/2 and -h <= dy <= 0.  A point exactly on a face is inside.
+ * box2d, frustum_angle, corners, out_pts and out_seg are what fcn_prepare_inputs takes as box2d, frustum_angle, corners, raw and seg
+ * (heading = ry, size = l, w, h).
+ * D == 0: returns 0, touches nothing.  F == 0: returns 0 (the count zeroes seg_cnt and seg_pos).  NULL pointers, pt_stride < 3,
+ * S < 1, D > 65535 and a frame longer than S * seg rows are FCN_E_BADARG with no launch; a box whose frame is out of range is never
+ * dereferenced -- its counts are 0, nothing else of it is written, the other boxes are processed and the call returns
+ * FCN_E_BADARG.  Both calls synchronise the stream, as the select pair does. */
+int fcn_frustum_label_count(const float *frame_pts, const int64_t *frame_off, int F, int pt_stride, const double *P,
+                            const double *V2C, const double *R0, const double *img_wh, const double *boxes,
+                            const int32_t *box_frame, int D, int S, int clip_boxes, double clip_distance, const double *gt_box3d,
+                            double *box2d, double *frustum_angle, int32_t *seg_cnt, int32_t *seg_pos, double *corners,
+                            void *stream);
+int fcn_frustum_label_fill(const float *frame_pts, const int64_t *frame_off, int F, int pt_stride, const double *P,
+                           const double *V2C, const double *R0, const double *img_wh, const double *boxes,
+                           const int32_t *box_frame, int D, int S, int clip_boxes, double clip_distance, const double *gt_box3d,
+                           const int64_t *seg_off, float *out_pts, int64_t *out_seg, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
