@@ -8,6 +8,10 @@ Here the selection is two HIP launches and the selected points go straight into 
 stages the host reads the first stage's keep lists, D point counts and D predicted widths, and each of the two entry points
 reads the 2 * D candidate indices back to range-check them (five small reads that wait for the stream; no point data).  No CPU
 fallback.
+
+Training the refinement stage on the first stage's output (extract_frustum_det_data :406-592: match to the labels, enlarge, jitter,
+select, count the positives, reject) is match_detections + draw_box3d_jitter + refine_training_candidates (C-ABI fcn_refine_match,
+fcn_refine_label_count / _fill, csrc/refine_label.h) and RefineInputBuilder.build_device_train.
 """
 import numpy as np
 import torch
@@ -58,6 +62,132 @@ def refine_candidates(frame_points, frame_off, dets, cand_row, cand_frame, ratio
     out["score"] = d8[:, 7].index_select(0, crow.to(torch.int64)) if D else d8[:0, 7]
     out["counts"] = counts
     return out
+
+
+
+def _candidates(who, frame_points, dets, cand_row, cand_frame):
+    """The device tensors the match and the labelled selection share: dets (R,8) float32, cand_row / cand_frame (D) int32."""
+    dev = frame_points.device
+    d8 = dets.detach().to(device=dev, dtype=torch.float32).contiguous()
+    if d8.dim() != 2 or d8.shape[1] != 8:
+        raise ValueError("%s: dets must be (R, 8), got %s" % (who, tuple(dets.shape)))
+    crow = torch.as_tensor(cand_row).to(device=dev, dtype=torch.int32).contiguous().view(-1)
+    cframe = torch.as_tensor(cand_frame).to(device=dev, dtype=torch.int32).contiguous().view(-1)
+    if crow.numel() != cframe.numel():
+        raise ValueError("%s: %d rows but %d frames" % (who, crow.numel(), cframe.numel()))
+    return d8, crow, cframe
+
+
+def match_detections(dets, cand_row, cand_frame, gt_box3d, gt_off, thresh):
+    """Matches first-stage detections to the label boxes of their frames (kitti/prepare_data_refine.py:483-499; C-ABI
+    fcn_refine_match).  dets (R,8) float32 label-format rows on the device, cand_row (D) / cand_frame (D) as refine_candidates
+    takes them; gt_box3d (G,7) tx, ty, tz, l, w, h, ry of every label box (t the bottom centre), frame after frame; gt_off (F+1)
+    int64: the label boxes of frame f are rows [gt_off[f], gt_off[f+1]); thresh: the reference uses 0.5 for Car and 0.25 otherwise.
+    Returns (gt_idx (D) int32, best_iou (D) float32) on the device: the row of gt_box3d with the largest 3-D IoU (the lowest row
+    among equal maxima), or -1 when the frame has no label box or the IoU is below thresh, and that IoU."""
+    _need_cuda(dets, "match_detections")
+    dev = dets.device
+    d8, crow, cframe = _candidates("match_detections", dets, dets, cand_row, cand_frame)
+    gt = torch.as_tensor(gt_box3d).to(device=dev, dtype=torch.float64).contiguous().view(-1, 7)
+    goff = torch.as_tensor(gt_off).to(device=dev, dtype=torch.int64).contiguous().view(-1)
+    D, F = int(crow.numel()), int(goff.numel()) - 1
+    gt_idx = torch.full((D,), -1, dtype=torch.int32, device=dev)
+    best = torch.zeros((D,), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        _native.check(_native.lib().fcn_refine_match(d8.data_ptr(), int(d8.shape[0]), crow.data_ptr(), cframe.data_ptr(), D,
+                                                     gt.data_ptr() if gt.numel() else None, int(gt.shape[0]), goff.data_ptr(), F,
+                                                     float(thresh), gt_idx.data_ptr(), best.data_ptr(),
+                                                     _native.current_stream(dev)), "fcn_refine_match")
+    return gt_idx, best
+
+
+def draw_box3d_jitter(n, augmentX, rng=np.random):
+    """The uniform draws of kitti/prepare_data_refine.py::random_shift_rotate_box3d (:203-236) for n candidates with augmentX
+    chained copies each: (n, augmentX, 7) float64 in the reference's order -- candidates outer, copies inner, seven rng.random()
+    per copy (l, h, w, cx, cy, cz, angle) -- so with the same seed the numbers are the reference's and the generator is left in
+    its state.  The reference draws for MATCHED candidates only: draw for those (gt_idx >= 0) and scatter the rows into the
+    (D, augmentX, 7) array refine_training_candidates takes; the rows of unmatched candidates are never read."""
+    out = np.empty((int(n), int(augmentX), 7), dtype=np.float64)
+    for i in range(int(n)):
+        for a in range(int(augmentX)):
+            for k in range(7):
+                out[i, a, k] = rng.random()
+    return out
+
+
+def refine_training_candidates(frame_points, frame_off, dets, cand_row, cand_frame, cand_gt, gt_box3d, jitter=None, ratio=1.2,
+                               shift_ratio=0.05):
+    """The refinement stage's TRAINING records from first-stage detections and their matched label boxes, on the device: what
+    kitti/prepare_data_refine.py::extract_frustum_det_data (:406-592) pickles.  frame_points ... cand_frame as refine_candidates
+    takes them; cand_gt (D) the row of gt_box3d matched to each candidate (match_detections), negative: unmatched, skipped;
+    gt_box3d (G,7) tx, ty, tz, l, w, h, ry; jitter (D,A,7) float64 uniform draws (draw_box3d_jitter) for A chained perturbed
+    copies per candidate, or None: one un-jittered copy.  Units are u = d * A + a.  A unit without a point inside its label box
+    is rejected (:547) and takes no room in the packed buffers.
+    With label boxes as dets rows and cand_gt = arange this is extract_frustum_data (:239-403).
+    Returns a dict over the K kept units: points (sum cnt, stride) float32; off (K+1) int64; pred_box3d (K,8,3), pred_angle (K),
+    pred_size (K,3) of the jittered enlarged box and box3d (K,8,3), heading (K), size (K,3) of the label box, fp64; cnt (K), pos
+    (K) int32 -- on the device -- and kept (K) int64 (unit indices), unit_cand (K) int64 (the candidate of each kept unit), counts
+    (K) int64 on the host.  With no kept unit the dict holds 'kept' alone.
+    The host reads the 2 * U * S selected and positive segment counts once, together, between the two launches."""
+    who = "refine_training_candidates"
+    _need_cuda(frame_points, who)
+    dev = frame_points.device
+    pts = frame_points.detach().contiguous().float()
+    if pts.dim() != 2 or pts.shape[1] < 3:
+        raise ValueError("%s: frame_points must be (n, >= 3), got %s" % (who, tuple(frame_points.shape)))
+    foff_h = torch.as_tensor(frame_off).detach().cpu().to(torch.int64).contiguous().view(-1)      # F + 1 integers: they decide S
+    foff = foff_h.to(dev, non_blocking=True)
+    d8, crow, cframe = _candidates(who, frame_points, dets, cand_row, cand_frame)
+    cgt = torch.as_tensor(cand_gt).to(device=dev, dtype=torch.int32).contiguous().view(-1)
+    gt = torch.as_tensor(gt_box3d).to(device=dev, dtype=torch.float64).contiguous().view(-1, 7)
+    F, R, D, G, ps = int(foff_h.numel()) - 1, int(d8.shape[0]), int(crow.numel()), int(gt.shape[0]), int(pts.shape[1])
+    if cgt.numel() != D:
+        raise ValueError("%s: %d candidates but %d cand_gt" % (who, D, cgt.numel()))
+    A, jit = 1, None
+    if jitter is not None:
+        jit = torch.as_tensor(jitter).to(device=dev, dtype=torch.float64).contiguous()
+        if jit.dim() != 3 or jit.shape[0] != D or jit.shape[2] != 7 or jit.shape[1] < 1:
+            raise ValueError("%s: jitter must be (%d, A >= 1, 7), got %s" % (who, D, tuple(jit.shape)))
+        A = int(jit.shape[1])
+    none = {"kept": np.zeros(0, dtype=np.int64)}
+    if D == 0 or F == 0 or G == 0:
+        return none
+    U = D * A
+    L = _native.lib()
+    seg = int(L.fcn_frustum_select_seg())
+    S = max(1, -(-int((foff_h[1:] - foff_h[:-1]).max()) // seg))
+    if pts.shape[0] == 0:
+        pts = torch.zeros((1, ps), dtype=torch.float32, device=dev)        # (an address to hand in: every frame is empty)
+    f64 = dict(dtype=torch.float64, device=dev)
+    pc, pa, psz = torch.zeros((U, 8, 3), **f64), torch.zeros((U,), **f64), torch.zeros((U, 3), **f64)
+    gc, gh, gs = torch.zeros((U, 8, 3), **f64), torch.zeros((U,), **f64), torch.zeros((U, 3), **f64)
+    both = torch.zeros((2, U, S), dtype=torch.int32, device=dev)            # selected, positive: one read
+    args = (pts.data_ptr(), foff.data_ptr(), F, ps, d8.data_ptr(), R, crow.data_ptr(), cframe.data_ptr(), D, float(ratio),
+            cgt.data_ptr(), gt.data_ptr(), G, A, None if jit is None else jit.data_ptr(), float(shift_ratio), S)
+    with torch.cuda.device(dev):
+        _native.check(L.fcn_refine_label_count(*args, both[0].data_ptr(), both[1].data_ptr(), pc.data_ptr(), pa.data_ptr(),
+                                               psz.data_ptr(), gc.data_ptr(), gh.data_ptr(), gs.data_ptr(),
+                                               _native.current_stream(dev)), "fcn_refine_label_count")
+        both_h = both.cpu().numpy().astype(np.int64)                        # 2 * U * S integers
+        seg_counts, positives = both_h[0], both_h[1].sum(1)
+        drop = positives == 0                                               # (an unmatched candidate's units count nothing)
+        kept = np.nonzero(~drop)[0].astype(np.int64)
+        if len(kept) == 0:
+            return {"kept": kept}
+        seg_counts[drop] = 0
+        seg_off = np.concatenate([[0], np.cumsum(seg_counts.reshape(-1))]).astype(np.int64)
+        soff = torch.from_numpy(seg_off).to(dev, non_blocking=True)
+        points = torch.empty((int(seg_off[-1]), ps), dtype=torch.float32, device=dev)
+        _native.check(L.fcn_refine_label_fill(*args, soff.data_ptr(), points.data_ptr(), _native.current_stream(dev)),
+                      "fcn_refine_label_fill")
+    idx = torch.from_numpy(kept).to(dev, non_blocking=True)
+    pick = lambda x: x.index_select(0, idx).contiguous()
+    # a rejected unit has no rows, so a kept unit ends where the next kept one starts
+    off = torch.cat([soff[::S][:U].index_select(0, idx), soff[-1:]])
+    return {"points": points, "off": off, "pred_box3d": pick(pc), "pred_angle": pick(pa), "pred_size": pick(psz),
+            "box3d": pick(gc), "heading": pick(gh), "size": pick(gs), "cnt": pick(both[0].sum(1, dtype=torch.int32)),
+            "pos": pick(both[1].sum(1, dtype=torch.int32)), "kept": kept, "unit_cand": kept // A,
+            "counts": seg_counts.sum(1)[kept]}
 
 
 class TwoStageDetector:

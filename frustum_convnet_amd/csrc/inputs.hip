@@ -432,3 +432,8 @@ extern "C" int fcn_prepare_inputs_refine(const fcn_inp_refine_desc *d, const flo
 // The same with one ground-truth 3-D box beside each 2-D box: the first stage's TRAINING records -- points, per-point foreground
 // labels, box corners (fcn_frustum_label_count / _fill): csrc/frustum_label.h
 #include "frustum_label.h"
+
+// ------------------------------------------------------------------------------------------------
+// First-stage detections + the frames' label boxes -> the refinement stage's TRAINING records: match, enlarge, jitter, select, count
+// the positives (fcn_refine_match, fcn_refine_label_count / _fill): csrc/refine_label.h
+#include "refine_label.h"

@@ -70,6 +70,16 @@ __device__ __forceinline__ bool rs_inside(const RsBox &b, float x, float y, floa
     return fabs(lx) <= b.hl && fabs(dy) <= b.hh && fabs(lz) <= b.hw;
 }
 
+// corner k of the box -> o[0..2].  compute_box_3d_obj_array: x = l/2 * (+ + - - + + - -), y = h/2 * (+ + + + - - - -),
+// z = w/2 * (+ - - + + - - +); roty(ry)
+__device__ __forceinline__ void rs_corner(const RsBox &b, int k, double *o)
+{
+    const double x = (k & 2) ? -b.hl : b.hl, y = (k & 4) ? -b.hh : b.hh, z = ((k + 1) & 2) ? -b.hw : b.hw;
+    o[0] = (b.c * x + b.s * z) + b.cx;
+    o[1] = y + b.cy;
+    o[2] = (-b.s * x + b.c * z) + b.cz;
+}
+
 // V4: pt_stride == 4 and 16-byte aligned rows -- one 16-byte load per point, which the fill stores back as it is
 template <bool V4> __device__ __forceinline__ bool rs_test(const RsArgs &a, const RsBox &b, int64_t row, float4 &v)
 {
@@ -111,14 +121,7 @@ template <bool V4> __global__ __launch_bounds__(RS_T) void rs_count_kernel(RsArg
         if (tid == 0) a.cnt[d] = 0;
         return;
     }
-    if (tid < 8) {
-        // compute_box_3d_obj_array: x = l/2 * (+ + - - + + - -), y = h/2 * (+ + + + - - - -), z = w/2 * (+ - - + + - - +); roty(ry)
-        const double x = (tid & 2) ? -b.hl : b.hl, y = (tid & 4) ? -b.hh : b.hh, z = ((tid + 1) & 2) ? -b.hw : b.hw;
-        double *o = a.corners + ((int64_t)d * 8 + tid) * 3;
-        o[0] = (b.c * x + b.s * z) + b.cx;
-        o[1] = y + b.cy;
-        o[2] = (-b.s * x + b.c * z) + b.cz;
-    }
+    if (tid < 8) rs_corner(b, tid, a.corners + ((int64_t)d * 8 + tid) * 3);
     if (tid == 0) {
         a.angle[d] = b.ry;
         a.size[3 * d] = b.l; a.size[3 * d + 1] = b.w; a.size[3 * d + 2] = b.h;

@@ -439,6 +439,36 @@ class RefineInputBuilder:
         out["kept"] = kept
         return out
 
+    def build_device_train(self, sel, types, draws=None):
+        """The TRAINING batch -- the dict of build(records, with_labels=True), same keys, shapes and dtypes -- straight from the
+        device tensors of cascade.refine_training_candidates: no point, corner or label box leaves the device.  sel: its dict;
+        types: the class name of each of the D CANDIDATES (a kept unit's is looked up through sel["unit_cand"]); draws: (choice
+        (K,N) int32, coin (K), normal (K)) for the K kept units, or None to draw like draw_refine from their counts under the
+        builder's random_flip / random_shift.  The host reads K numbers here: the predicted widths, which decide the padded
+        window counts.  ONE launch of fcn_prepare_inputs_refine.  With no kept unit the dict holds 'kept' alone."""
+        if self.device.type != "cuda":
+            raise RuntimeError("frustum_convnet_amd: input construction is a HIP kernel (MI355X only); no CPU fallback")
+        kept = np.asarray(sel["kept"], dtype=np.int64)
+        K = len(kept)
+        if K == 0:
+            return {"kept": kept}
+        if draws is None:
+            draws = draw_refine(sel["counts"], self.npoints, self.random_flip, self.random_shift)
+        choice, coin, normal = draws
+        dev = self.device
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev, non_blocking=True)
+        widths = sel["pred_size"][:, 1].cpu().numpy()                         # K numbers: the tensor shapes depend on them
+        t = {"raw": sel["points"], "off": sel["off"], "choice": up(np.asarray(choice, dtype=np.int32)),
+             "pcorners": sel["pred_box3d"].reshape(K, 24), "pangle": sel["pred_angle"], "psize": sel["pred_size"],
+             "corners": sel["box3d"].reshape(K, 24), "heading": sel["heading"], "size": sel["size"],
+             "coin": up(np.asarray(coin, dtype=np.float64)), "normal": up(np.asarray(normal, dtype=np.float64))}
+        out = self._launch(t, K, int(sel["points"].shape[1]), self._lpad(widths), True)
+        size_class = [self.classes.index(types[i]) for i in sel["unit_cand"]]
+        out["size_class"] = torch.tensor(size_class, dtype=torch.int64).view(K, 1).to(dev, non_blocking=True)
+        if self.one_hot:
+            out["one_hot"] = self._one_hot(size_class)
+        return out
+
     def build(self, records, draws=None, with_labels=True):
         """records: dicts with REFINE_KEYS (points (n,>=3) float32 rect camera coordinates; box3d (8,3), heading, size (l,w,h)
         of the label box; pred_box3d (8,3), pred_angle, pred_size of the first-stage prediction; type).  Returns the batch

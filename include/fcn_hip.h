@@ -645,6 +645,53 @@ int fcn_frustum_label_fill(const float *frame_pts, const int64_t *frame_off, int
                            const int32_t *box_frame, int D, int S, int clip_boxes, double clip_distance, const double *gt_box3d,
                            const int64_t *seg_off, float *out_pts, int64_t *out_seg, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * The cascade link for TRAINING the refinement stage: first-stage detections + the frames' label boxes -> the labelled raw
+ * records fcn_prepare_inputs_refine takes.  Replaces the host loop of kitti/prepare_data_refine.py::extract_frustum_det_data
+ * (:406-592) and, with the label boxes themselves as detections, of extract_frustum_data (:239-403).
+ *   frame_pts, frame_off, F, pt_stride, dets (R,8), cand_row (D), cand_frame (D), ratio: as fcn_refine_select_count takes them;
+ *   gt_box3d (G,7) fp64 = tx, ty, tz, l, w, h, ry as a KITTI label file has them (t the centre of the BOTTOM face).
+ * fcn_refine_match: gt_off (F+1) int64 -- the label boxes of frame f are rows [gt_off[f], gt_off[f+1]) of gt_box3d.  Per candidate
+ *   the 3-D IoU of its centre form (tx, ty - h/2, tz, l, w, h, ry) against every label box of its frame (the float32 clip core of
+ *   the NMS, on the label box taken relative to the candidate's centre in fp64), best_iou (D) float32 = the largest (0 for a frame
+ *   without label boxes) and gt_idx (D) int32 = its row of gt_box3d, the LOWEST row among equal maxima, or -1 when the frame has no
+ *   label box or !(best_iou >= thresh) (:493-499; a NaN matches nothing).  rbbox_iou_3d's standup-box prefilter only zeroes pairs
+ *   whose IoU is 0 anyway and is not restated.
+ * fcn_refine_label_count / _fill: units u = d * A + a, candidate d, copy a of A (1 <= A <= 64, D * A <= 65535); cand_gt (D) int32 =
+ *   the label row of each candidate, negative: its units are empty (counts 0, nothing else written).  The enlarged box of unit u
+ *   is candidate d's box times ratio, then jitter steps 0..a of random_shift_rotate_box3d (:203-236) with r = shift_ratio, each on
+ *   the result of the one before (the reference's copies chain, :513-519), from jitter (D,A,7) fp64 uniform draws in [0,1) in the
+ *   reference's order l, h, w, cx, cy, cz, angle: l1 = l + l*r*(u*2-1) (h1, w1 likewise), cx1 = cx + l*r*(u*2-1), cy1 = cy +
+ *   h*r*(u*2-1), cz1 = cz + w*r*(u*2-1), angle1 = ((ry + pi) + r*(u*2-1)*pi) mod 2 pi (floored) - pi.  jitter == NULL: no jitter,
+ *   A must be 1, and the boxes, counts and rows are fcn_refine_select_count / _fill's bit for bit.
+ *   The grid is (S, D * A) over the segments of fcn_frustum_select_seg() rows; S >= ceil(max m_f / seg).
+ *   count writes seg_cnt (D*A,S) int32 = the rows of the segment inside the unit's enlarged box, seg_pos (D*A,S) int32 = those of
+ *   them inside the label box (NOT enlarged; centre (tx, ty - h/2, tz)), and per unit pred_corners (D*A,8,3), pred_angle, pred_size
+ *   (D*A,3) of the jittered enlarged box, gt_corners (D*A,8,3), gt_heading, gt_size (D*A,3) of the label box -- both corner sets in
+ *   the order of compute_box_3d_obj_array: what fcn_prepare_inputs_refine takes as pred_corners, pred_angle, pred_size,
+ *   box3d_corners, heading, size.
+ *   fill takes seg_off (D*A*S+1) int64 -- the caller's ONE cumulative sum over the flattened counts, with the counts of a rejected
+ *   unit (no positive: :547) set to 0 first -- and writes out_pts as fcn_refine_select_fill does: bit-exact copies of all pt_stride
+ *   floats, ascending frame order, a row outside its workgroup's slice [seg_off[i], seg_off[i+1]) dropped, never stored.
+ * Inside, for both boxes: fcn_refine_select_count's closed box in fp64 from the fp32 row; a non-finite row is never inside.  The
+ * per-point label is not written: the refinement loader never reads it.
+ * D == 0: returns 0, touches nothing.  F == 0: returns 0 (match: gt_idx = -1, best_iou = 0; count: both counts zeroed).  NULL
+ * pointers, pt_stride < 3, S < 1, A out of range, NULL jitter with A != 1, D * A > 65535 and a frame longer than S * seg rows are
+ * FCN_E_BADARG with no launch.  A candidate whose row or frame is out of range, or whose cand_gt >= G, is never dereferenced: its
+ * counts are 0 (match: gt_idx = -1), nothing else of it is written, the others are processed and the call returns FCN_E_BADARG.
+ * All three calls read their index lists back first (a stream synchronisation: NOT capturable into a hipGraph). */
+int fcn_refine_match(const float *dets, int R, const int32_t *cand_row, const int32_t *cand_frame, int D, const double *gt_box3d,
+                     int G, const int64_t *gt_off, int F, double thresh, int32_t *gt_idx, float *best_iou, void *stream);
+int fcn_refine_label_count(const float *frame_pts, const int64_t *frame_off, int F, int pt_stride, const float *dets, int R,
+                           const int32_t *cand_row, const int32_t *cand_frame, int D, double ratio, const int32_t *cand_gt,
+                           const double *gt_box3d, int G, int A, const double *jitter, double shift_ratio, int S,
+                           int32_t *seg_cnt, int32_t *seg_pos, double *pred_corners, double *pred_angle, double *pred_size,
+                           double *gt_corners, double *gt_heading, double *gt_size, void *stream);
+int fcn_refine_label_fill(const float *frame_pts, const int64_t *frame_off, int F, int pt_stride, const float *dets, int R,
+                          const int32_t *cand_row, const int32_t *cand_frame, int D, double ratio, const int32_t *cand_gt,
+                          const double *gt_box3d, int G, int A, const double *jitter, double shift_ratio, int S,
+                          const int64_t *seg_off, float *out_pts, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
