@@ -390,7 +390,15 @@ class RefineInputBuilder:
         return out
 
     def _lpad(self, widths):
-        """Batch maxima of len(np.arange(-w/2, w/2, s)) over the predicted widths: the padded widths of the outputs."""
+        """Batch maxima of len(np.arange(-w/2, w/2, s)) over the predicted widths: the padded widths of the outputs.
+        A width that is not a positive finite number (untrained first-stage weights can decode one) has no window on any
+        stride: the reference's collate cannot pad such a sample, and the kernel would leave its cls_label row unwritten --
+        refused here, where build(), build_device() and build_device_train() all pass."""
+        widths = np.asarray(widths, dtype=np.float64).reshape(-1)
+        for i, w in enumerate(widths):
+            if not (w > 0.0 and np.isfinite(w)):
+                raise ValueError("RefineInputBuilder: sample %d has predicted width %r: no window on any stride "
+                                 "(fcn_prepare_inputs_refine needs every pred_size width > 0)" % (i, float(w)))
         return [int(max(len(np.arange(-w / 2.0, w / 2.0, s)) for w in widths)) for s in self.strides]
 
     def _one_hot(self, size_class):

@@ -536,7 +536,11 @@ int fcn_prepare_inputs_sunrgbd(const fcn_inp5_desc *d, const float *raw_pts, con
  * repeating the last real entry, as the reference's collate_fn does (Lpad = the batch maxima, computed by the caller as
  * max_b len(np.arange(-w_b/2, w_b/2, stride[s]))); lens (B,4) receives the per-sample counts.  box3d_corners == NULL:
  * inference records (no labels; cls_label / box3d_* must be NULL).  Outputs rot_angle (B,1) = pred_angle and
- * ref_center (B,3) = predicted centre are what from_prediction_to_label_format needs to undo the normalisation. */
+ * ref_center (B,3) = predicted centre are what from_prediction_to_label_format needs to undo the normalisation.
+ * PRECONDITION (the caller's: the widths live on the device, this call does not read them on the host): every pred_size width
+ * (pred_size[3 b + 1]) is finite and > 0.  A sample whose width is <= 0 or NaN has no window on any stride: its lens are 0, its
+ * center_ref rows are not meaningful and its cls_label row is NOT written.  frustum_convnet_amd.inputs.RefineInputBuilder
+ * refuses such a batch with ValueError before the launch. */
 typedef struct fcn_inp_refine_desc {
     int32_t B, N, pt_stride;
     int32_t Lpad[4];

@@ -187,6 +187,26 @@ CASES = [
     ("test_gpu_front_edges", "test_refusals_return_their_code_and_launch_nothing", ()),
 ]
 
+# the batch-builder kernels off their fixtures: every case of the module (the case names come from tests/inputs_cases.py)
+import inputs_cases  # noqa: E402
+
+CASES += [("test_gpu_inputs_edges", "test_refine_case", (n,)) for n in inputs_cases.REFINE_CASES]
+CASES += [("test_gpu_inputs_edges", "test_first_stage_case", (n,)) for n in inputs_cases.KITTI_CASES]
+CASES += [("test_gpu_inputs_edges", "test_sunrgbd_matrix", (n,)) for n in inputs_cases.SUNRGBD_CASES]
+CASES += [
+    ("test_gpu_inputs_edges", "test_refine_inference_form", ()),
+    ("test_gpu_inputs_edges", "test_refine_every_element_written", ("fallback_last_padded-off",)),
+    ("test_gpu_inputs_edges", "test_refine_every_element_written", ("fallback_last_padded-on",)),
+    ("test_gpu_inputs_edges", "test_kitti_infer_entry", ()),
+    ("test_gpu_inputs_edges", "test_refusals_leave_the_outputs_alone", ("fcn_prepare_inputs",)),
+    ("test_gpu_inputs_edges", "test_refusals_leave_the_outputs_alone", ("fcn_prepare_inputs_infer",)),
+    ("test_gpu_inputs_edges", "test_refusals_leave_the_outputs_alone", ("fcn_prepare_inputs_sunrgbd",)),
+    ("test_gpu_inputs_edges", "test_refusals_leave_the_outputs_alone", ("fcn_prepare_inputs_refine",)),
+]
+for _path in ("build", "build_infer", "build_device", "build_device_train"):
+    CASES += [("test_gpu_inputs_edges", "test_a_sample_without_a_window_is_refused", (_path, (1.6, -0.3, 0.0), 1, "-0.3")),
+              ("test_gpu_inputs_edges", "test_a_sample_without_a_window_is_refused", (_path, (1.6, 0.9, float("nan")), 2, "nan"))]
+
 
 def _ident(c):
     a = c[2]
