@@ -83,7 +83,7 @@ class InpRefineDesc(ctypes.Structure):
 
 EXPORTS = ("fcn_arch", "fcn_build_hash", "fcn_stat_replicas", "fcn_query_depth_point_f32", "fcn_query_depth_point_multi_f32", "fcn_pn_wgrad_rows", "fcn_pn_compact", "fcn_pn_group_compact", "fcn_pn_group_compact2",
            "fcn_pn_pack_weights", "fcn_pn_pack_weights_all", "fcn_pn_infer_fold", "fcn_pn_infer", "fcn_pn_forward", "fcn_pn_backward", "fcn_pn_backward2", "fcn_pn_backward3", "fcn_pn_backward_dense", "fcn_pn_conv_fwd", "fcn_det_loss_tail", "fcn_det_loss_tail_rows", "fcn_det_loss_tail_rows2", "fcn_det_iou_metrics",
-           "fcn_det_loss_tail_scratch_floats", "fcn_adam_step_f32", "fcn_sgd_step_f32", "fcn_adam_step_slots", "fcn_prepare_inputs", "fcn_prepare_inputs_refine", "fcn_prepare_inputs_sunrgbd", "fcn_refine_select_count", "fcn_refine_select_fill", "fcn_prepare_inputs_infer", "fcn_frustum_select_seg", "fcn_frustum_select_count", "fcn_frustum_select_fill", "fcn_frustum_label_count", "fcn_frustum_label_fill", "fcn_refine_match", "fcn_refine_label_count", "fcn_refine_label_fill", "fcn_stamp", "fcn_stream_capture_id",
+           "fcn_det_loss_tail_scratch_floats", "fcn_adam_step_f32", "fcn_sgd_step_f32", "fcn_adam_step_slots", "fcn_prepare_inputs", "fcn_prepare_inputs_refine", "fcn_prepare_inputs_sunrgbd", "fcn_refine_select_count", "fcn_refine_select_fill", "fcn_prepare_inputs_infer", "fcn_frustum_select_seg", "fcn_frustum_select_count", "fcn_frustum_select_fill", "fcn_frustum_label_count", "fcn_frustum_label_fill", "fcn_frustum_sunrgbd_count", "fcn_frustum_sunrgbd_fill", "fcn_frustum_sunrgbd_label_count", "fcn_frustum_sunrgbd_label_fill", "fcn_frustum_subset_pos", "fcn_prepare_inputs_sunrgbd_infer", "fcn_refine_match", "fcn_refine_label_count", "fcn_refine_label_fill", "fcn_stamp", "fcn_stream_capture_id",
            "fcn_convnet_sizes", "fcn_convnet_logits_ld", "fcn_convnet_pack", "fcn_convnet_forward", "fcn_convnet_forward2",
            "fcn_convnet_backward", "fcn_box3d_iou_pair_f32", "fcn_decode_detections", "fcn_rotate_nms_3d")
 
@@ -195,6 +195,19 @@ def lib():
     L.fcn_frustum_label_count.argtypes = fs_in + [c_fp] * 7
     L.fcn_frustum_label_fill.restype = ctypes.c_int
     L.fcn_frustum_label_fill.argtypes = fs_in + [c_fp] * 5
+    sr_in = [c_fp, c_fp, ctypes.c_int, ctypes.c_int] + [c_fp] * 4 + [ctypes.c_int] * 2
+    L.fcn_frustum_sunrgbd_count.restype = ctypes.c_int
+    L.fcn_frustum_sunrgbd_count.argtypes = sr_in + [c_fp] * 3
+    L.fcn_frustum_sunrgbd_fill.restype = ctypes.c_int
+    L.fcn_frustum_sunrgbd_fill.argtypes = sr_in + [c_fp] * 3
+    L.fcn_frustum_sunrgbd_label_count.restype = ctypes.c_int
+    L.fcn_frustum_sunrgbd_label_count.argtypes = sr_in + [c_fp] * 6
+    L.fcn_frustum_sunrgbd_label_fill.restype = ctypes.c_int
+    L.fcn_frustum_sunrgbd_label_fill.argtypes = sr_in + [c_fp] * 5
+    L.fcn_frustum_subset_pos.restype = ctypes.c_int
+    L.fcn_frustum_subset_pos.argtypes = [c_fp] * 5 + [ctypes.c_int] + [c_fp] * 2
+    L.fcn_prepare_inputs_sunrgbd_infer.restype = ctypes.c_int
+    L.fcn_prepare_inputs_sunrgbd_infer.argtypes = [ctypes.POINTER(Inp5Desc)] + [c_fp] * 8 + [c_fp * 5] + [c_fp] * 2
     L.fcn_refine_match.restype = ctypes.c_int
     L.fcn_refine_match.argtypes = ([c_fp, ctypes.c_int, c_fp, c_fp, ctypes.c_int, c_fp, ctypes.c_int, c_fp, ctypes.c_int,
                                     ctypes.c_double] + [c_fp] * 3)

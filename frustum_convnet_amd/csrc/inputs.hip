@@ -258,6 +258,32 @@ extern "C" int fcn_prepare_inputs_sunrgbd(const fcn_inp5_desc *d, const float *r
     return 0;
 }
 
+// Inference records of the SUN-RGBD loader (provider_sample_sunrgbd.py:165-186, from_rgb_detection): the same kernel with
+// corners == nullptr, as fcn_prepare_inputs_infer has it -- point_cloud, center_ref[5] and rot_angle alone.
+extern "C" int fcn_prepare_inputs_sunrgbd_infer(const fcn_inp5_desc *d, const float *raw_pts, const int64_t *pt_off,
+                                                const int32_t *choice, const double *frustum_angle, const double *box2d,
+                                                const double *K, const double *Rtilt, float *point_cloud,
+                                                float *const center_ref[5], float *rot_angle, void *stream)
+{
+    if (!d || !raw_pts || !pt_off || !choice || !frustum_angle || !box2d || !K || !Rtilt || !point_cloud || !center_ref || !rot_angle)
+        return FCN_E_BADARG;
+    if (d->B <= 0 || d->N <= 0 || d->pt_stride < 3 || d->random_flip || d->random_shift) return FCN_E_BADARG;
+    for (int s = 0; s < 5; ++s)
+        if (d->L[s] <= 0 || !(d->stride[s] > 0.0) || !center_ref[s]) return FCN_E_BADARG;
+    InpArgs a;
+    a.d.B = d->B; a.d.N = d->N; a.d.pt_stride = d->pt_stride; a.d.nsc = 5; a.d.max_depth = d->max_depth;
+    a.d.random_flip = 0; a.d.random_shift = 0;
+    for (int s = 0; s < 5; ++s) { a.d.L[s] = d->L[s]; a.d.stride[s] = d->stride[s]; a.ref[s] = center_ref[s]; }
+    a.raw = raw_pts; a.off = pt_off; a.raw_seg = nullptr; a.choice = choice; a.fangle = frustum_angle;
+    a.box2d = box2d; a.P = nullptr; a.corners = nullptr; a.heading = nullptr; a.size = nullptr; a.coin = nullptr; a.normal = nullptr;
+    a.K = K; a.Rtilt = Rtilt; a.hshift = nullptr;
+    a.pc = point_cloud;
+    a.cls = nullptr; a.center = nullptr; a.head = nullptr; a.osize = nullptr; a.rot = rot_angle; a.seg = nullptr;
+    hipLaunchKernelGGL(prepare_inputs_kernel, dim3(d->B), dim3(INP_T), 0, (hipStream_t)stream, a);
+    FCN_CHECK_LAUNCH();
+    return 0;
+}
+
 // ------------------------------------------------------------------------------------------------
 // Refinement stage (cfgs/refine_car.yaml; datasets/provider_sample_refine.py::ProviderDataset.__getitem__ :176-315 with
 // get_center_view_point / _box3d :137-152, generate_ref :336-386, generate_labels :317-334, and collate_fn :388-419).  The
@@ -432,6 +458,11 @@ extern "C" int fcn_prepare_inputs_refine(const fcn_inp_refine_desc *d, const flo
 // The same with one ground-truth 3-D box beside each 2-D box: the first stage's TRAINING records -- points, per-point foreground
 // labels, box corners (fcn_frustum_label_count / _fill): csrc/frustum_label.h
 #include "frustum_label.h"
+
+// ------------------------------------------------------------------------------------------------
+// The SUN-RGBD front: upright-depth frames + K + Rtilt + 2-D boxes (+ a label 3-D box beside each) -> the raw records of the
+// five-scale model (fcn_frustum_sunrgbd_count / _fill, _label_count / _label_fill, fcn_frustum_subset_pos): csrc/frustum_sunrgbd.h
+#include "frustum_sunrgbd.h"
 
 // ------------------------------------------------------------------------------------------------
 // First-stage detections + the frames' label boxes -> the refinement stage's TRAINING records: match, enlarge, jitter, select, count

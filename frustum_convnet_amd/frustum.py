@@ -2,6 +2,9 @@
 stage's raw frustum points and the refine stage's search set (C-ABI fcn_frustum_select_count / _fill, csrc/frustum_select.h), and,
 with a ground-truth 3-D box beside each 2-D box, the first stage's training records: points, per-point labels, corners
 (fcn_frustum_label_count / _fill, csrc/frustum_label.h; kitti/prepare_data.py::extract_frustum_data :260-391 in the reference).
+The SUN-RGBD configuration has the same two paths from upright-depth frames, K and Rtilt (sunrgbd_candidates,
+sunrgbd_training_candidates; fcn_frustum_sunrgbd_count / _fill / _label_count / _label_fill, csrc/frustum_sunrgbd.h;
+sunrgbd/prepare_data.py::extract_frustum_data :132-267 and extract_frustum_data_from_rgb_detection :270-381 in the reference).
 
 Reference: kitti/prepare_data.py::extract_frustum_data_rgb_detection (:462-568) projects the whole frame to the image once per
 frame in numpy (kitti_util.Calibration.project_velo_to_rect / project_rect_to_image, draw_util.get_lidar_in_image_fov) and masks
@@ -195,3 +198,200 @@ def frustum_training_candidates(frame_points, frame_off, calib, img_size, boxes2
             "heading": pick(gt[:, 6]), "size": pick(gt[:, 3:6]), "box_frame": pick(bframe),
             "cnt": pick(both[0].sum(1, dtype=torch.int32)), "pos": pick(both[1].sum(1, dtype=torch.int32)),
             "kept": kept, "counts": seg_counts.sum(1)[kept]}
+
+
+# ------------------------------------------------------------------------------------------------
+# SUN-RGBD: upright-depth frames (xyz + rgb), per-frame K and Rtilt, 2-D boxes (csrc/frustum_sunrgbd.h)
+SUNRGBD_CAP = 2048                     # sunrgbd/prepare_data.py:220, :346: a frustum of more rows is subsampled to this many
+SUNRGBD_MIN = 5                        # :226 (positives, training), :352 (rows, detections)
+
+
+def perturb_boxes2d_sunrgbd(boxes2d, shift_ratio=0.1, rng=np.random):
+    """sunrgbd/sunrgbd_utils.py::random_shift_box2d (:208-221) for D boxes in order: the centre moves by up to shift_ratio of the
+    width / height, both scale by 1 +- shift_ratio.  Four rng.random() draws per box in the reference's order, no clip, no retry:
+    with the same seed the boxes equal the reference's bit for bit and the generator is left in the reference's state.  augmentX
+    perturbed copies of a box: repeat its row.  Returns (D,4) float64 (host)."""
+    boxes = np.asarray(boxes2d, dtype=np.float64).reshape(-1, 4)
+    r = shift_ratio
+    out = np.empty_like(boxes)
+    for d, (xmin, ymin, xmax, ymax) in enumerate(boxes.tolist()):
+        h, w = ymax - ymin, xmax - xmin
+        cx, cy = (xmin + xmax) / 2.0, (ymin + ymax) / 2.0
+        cx2 = cx + w * r * (rng.random() * 2 - 1)
+        cy2 = cy + h * r * (rng.random() * 2 - 1)
+        h2 = h * (1 + rng.random() * 2 * r - r)
+        w2 = w * (1 + rng.random() * 2 * r - r)
+        out[d] = [cx2 - w2 / 2.0, cy2 - h2 / 2.0, cx2 + w2 / 2.0, cy2 + h2 / 2.0]
+    return out
+
+
+def draw_frustum_subsample(counts, cap=SUNRGBD_CAP, rng=np.random):
+    """The reference's subsample of a large frustum (sunrgbd/prepare_data.py:219-224, :345-349): per box, in order, one
+    rng.choice(n, cap, replace=False) when the box selects n > cap rows, else None (no draw).  Returns a list of D entries."""
+    return [rng.choice(int(n), cap, replace=False) if int(n) > cap else None for n in counts]
+
+
+def _check_sub(who, sub, counts):
+    """Host-made subsample indices are range-checked here, before any of them is uploaded."""
+    if len(sub) != len(counts):
+        raise ValueError("%s: %d subsamples for %d boxes" % (who, len(sub), len(counts)))
+    out = []
+    for d, (ix, n) in enumerate(zip(sub, counts)):
+        if ix is None:
+            out.append(None)
+            continue
+        ix = np.asarray(ix)
+        if ix.ndim != 1 or ix.dtype.kind not in "iu" or len(ix) == 0:
+            raise ValueError("%s: sub[%d] must be a non-empty 1-D integer array" % (who, d))
+        if int(ix.min()) < 0 or int(ix.max()) >= int(n):
+            raise ValueError("%s: sub[%d] indexes outside the box's %d rows" % (who, d, int(n)))
+        out.append(ix.astype(np.int32))
+    return out
+
+
+def subsampled_counts(counts, sub):
+    """Rows of each record: the length of its subsample where it has one, else its selected rows."""
+    return np.asarray([int(n) if ix is None else len(ix) for n, ix in zip(counts, sub)], dtype=np.int64)
+
+
+def _setup_sunrgbd(who, frame_points, frame_off, K, Rtilt, boxes2d, box_frame):
+    """The arguments the four entry points share (sr_in of _native.py), the tensors that back them, and ps, D, S."""
+    _need_cuda(frame_points, who)
+    dev = frame_points.device
+    pts = frame_points.detach().contiguous().float()
+    if pts.dim() != 2 or pts.shape[1] < 3:
+        raise ValueError("%s: frame_points must be (n, >= 3), got %s" % (who, tuple(frame_points.shape)))
+    foff_h = torch.as_tensor(frame_off).detach().cpu().to(torch.int64).contiguous().view(-1)      # F + 1 integers: they decide S
+    foff = foff_h.to(dev, non_blocking=True)
+    F, ps = int(foff_h.numel()) - 1, int(pts.shape[1])
+    cal = []
+    for name, m in (("K", K), ("Rtilt", Rtilt)):
+        t = torch.as_tensor(m).to(device=dev, dtype=torch.float64).contiguous()
+        if t.numel() != F * 9:
+            raise ValueError("%s: %s must hold %d x 9 numbers, got %s" % (who, name, F, tuple(t.shape)))
+        cal.append(t.view(F, 9))
+    boxes = torch.as_tensor(boxes2d).to(device=dev, dtype=torch.float64).contiguous().view(-1, 4)
+    bframe = torch.as_tensor(box_frame).to(device=dev, dtype=torch.int32).contiguous().view(-1)
+    D = int(bframe.numel())
+    if boxes.shape[0] != D:
+        raise ValueError("%s: %d boxes but %d frames" % (who, boxes.shape[0], D))
+    seg = int(_native.lib().fcn_frustum_select_seg())
+    longest = int((foff_h[1:] - foff_h[:-1]).max()) if F > 0 else 0
+    S = max(1, -(-longest // seg))
+    if pts.shape[0] == 0:
+        pts = torch.zeros((1, ps), dtype=torch.float32, device=dev)        # (an address to hand in: every frame is empty)
+    args = (pts.data_ptr(), foff.data_ptr(), F, ps, cal[0].data_ptr(), cal[1].data_ptr(), boxes.data_ptr(), bframe.data_ptr(), D, S)
+    return args, (pts, foff, cal[0], cal[1], boxes, bframe), ps, D, S
+
+
+def sunrgbd_candidates(frame_points, frame_off, K, Rtilt, boxes2d, box_frame, sub=None, cap=SUNRGBD_CAP, rng=np.random):
+    """The SUN-RGBD inference side (extract_frustum_data_from_rgb_detection :270-381).  frame_points (sum m_f, stride >= 3)
+    float32 UPRIGHT DEPTH x, y, z (+ r, g, b, ...) of F frames packed behind each other, frame_off (F+1) int64, K (F,3,3) and
+    Rtilt (F,3,3) float64, boxes2d (D,4) xmin ymin xmax ymax -- used as given, the reference does not clip them -- and box_frame
+    (D): device tensors (everything but the points may be host arrays).
+    Returns a dict: points (sum cnt, stride) -- per box, in frame order, the frame's rows that project into it, as upright
+    CAMERA (x, -z, y) followed by the untouched columns; off (D+1) int64; box2d (D,4) fp64 (the boxes, unrounded: :357);
+    frustum_angle (D) fp64; cnt (D) int32; box_frame (D) int32 -- on the device -- and, on the host, counts (D) int64 and sub: per
+    box the reference's subsample of a frustum of more than `cap` rows (row indices into the box's slice of `points`, drawn by
+    draw_frustum_subsample(counts, cap, rng) when not given, range-checked when given) or None.  The subsample is NOT applied to
+    `points`: SunrgbdInputBuilder.build_device composes it with its own draw.  The host reads the D * S segment counts once."""
+    who = "sunrgbd_candidates"
+    args, held, ps, D, S = _setup_sunrgbd(who, frame_points, frame_off, K, Rtilt, boxes2d, box_frame)
+    dev = frame_points.device
+    L = _native.lib()
+    out = {"box2d": held[4], "frustum_angle": torch.zeros((D,), dtype=torch.float64, device=dev), "box_frame": held[5]}
+    scnt = torch.zeros((D, S), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        _native.check(L.fcn_frustum_sunrgbd_count(*args, out["frustum_angle"].data_ptr(), scnt.data_ptr(),
+                                                  _native.current_stream(dev)), "fcn_frustum_sunrgbd_count")
+        seg_counts = scnt.cpu().numpy().astype(np.int64)                    # D * S integers: the size of `points`
+        counts = seg_counts.sum(1)
+        sub = draw_frustum_subsample(counts, cap, rng) if sub is None else _check_sub(who, sub, counts)
+        seg_off = np.concatenate([[0], np.cumsum(seg_counts.reshape(-1))]).astype(np.int64)
+        soff = torch.from_numpy(seg_off).to(dev, non_blocking=True)
+        out["points"] = torch.empty((int(seg_off[-1]), ps), dtype=torch.float32, device=dev)
+        if seg_off[-1] > 0:
+            _native.check(L.fcn_frustum_sunrgbd_fill(*args, soff.data_ptr(), out["points"].data_ptr(),
+                                                     _native.current_stream(dev)), "fcn_frustum_sunrgbd_fill")
+    out["off"] = soff[::S].contiguous()                                     # every S-th entry is a box's offset
+    out["cnt"] = scnt.sum(1, dtype=torch.int32)
+    out["counts"] = counts
+    out["sub"] = sub
+    return out
+
+
+def sunrgbd_training_candidates(frame_points, frame_off, K, Rtilt, boxes2d, box_frame, gt_box3d, sub=None, cap=SUNRGBD_CAP,
+                                min_positives=SUNRGBD_MIN, rng=np.random):
+    """The SUN-RGBD TRAINING records (extract_frustum_data :132-267), on the device.  frame_points ... box_frame as
+    sunrgbd_candidates takes them; boxes2d (D,4): the boxes that select -- perturbed (perturb_boxes2d_sunrgbd) or plain;
+    gt_box3d (D,7): cx, cy, cz, l, w, h, heading of the label beside each box in UPRIGHT DEPTH, l w h the label file's HALF
+    extents (SUNObject3d.l / .w / .h), heading = SUNObject3d.heading_angle.
+    The reference subsamples a frustum of more than `cap` rows and rejects a box with fewer than min_positives labelled rows
+    AFTER that (:219-227).  Here: a box whose full positive count is below the bar is dropped before the fill (it cannot pass);
+    after it fcn_frustum_subset_pos counts the positives the subsamples keep and the boxes below the bar are dropped too --
+    their rows stay in `points`, unlisted.  sub: as sunrgbd_candidates (one entry per box, all D of them, in order).
+    Returns a dict over the K kept boxes: points (rows, stride) float32 upright camera + the untouched columns and seg (rows)
+    int64; off (K+1) int64 -- off[k] is box k's FIRST row (its rows are off[k] ... off[k] + cnt[k]; the last entry is the end of
+    the buffer); box2d (K,4) fp64 = the float32 value the reference records (:230), widened -- selection and the frustum angle use
+    the unrounded box; frustum_angle (K), box3d (K,8,3) upright camera corners, heading (K), size (K,3) = 2l, 2w, 2h fp64;
+    box_frame (K), cnt (K), pos (K) int32 (the positives of the record, after its subsample) -- on the device -- and, on the host,
+    kept (K) int64, counts (K) int64 and sub (K entries).  With no survivor the dict holds 'kept' alone.
+    The host reads the 2 * D * S segment counts once, and one integer per pre-kept box when any of them is subsampled."""
+    who = "sunrgbd_training_candidates"
+    args, held, ps, D, S = _setup_sunrgbd(who, frame_points, frame_off, K, Rtilt, boxes2d, box_frame)
+    dev = frame_points.device
+    boxes, bframe = held[4], held[5]
+    gt = torch.as_tensor(gt_box3d).to(device=dev, dtype=torch.float64).contiguous().view(-1, 7)
+    if gt.shape[0] != D:
+        raise ValueError("%s: %d boxes, %d gt_box3d" % (who, D, gt.shape[0]))
+    if D == 0:
+        return {"kept": np.zeros(0, dtype=np.int64)}
+    L = _native.lib()
+    f64 = dict(dtype=torch.float64, device=dev)
+    angle, corners = torch.zeros((D,), **f64), torch.zeros((D, 8, 3), **f64)
+    both = torch.zeros((2, D, S), dtype=torch.int32, device=dev)            # selected, positive: one read
+    with torch.cuda.device(dev):
+        _native.check(L.fcn_frustum_sunrgbd_label_count(*args, gt.data_ptr(), angle.data_ptr(), both[0].data_ptr(),
+                                                        both[1].data_ptr(), corners.data_ptr(), _native.current_stream(dev)),
+                      "fcn_frustum_sunrgbd_label_count")
+        both_h = both.cpu().numpy().astype(np.int64)                        # 2 * D * S integers
+        seg_counts, positives = both_h[0], both_h[1].sum(1)
+        counts = seg_counts.sum(1)
+        sub = draw_frustum_subsample(counts, cap, rng) if sub is None else _check_sub(who, sub, counts)
+        drop = positives < min_positives
+        kept = np.nonzero(~drop)[0].astype(np.int64)
+        if len(kept) == 0:
+            return {"kept": kept}
+        seg_counts[drop] = 0
+        seg_off = np.concatenate([[0], np.cumsum(seg_counts.reshape(-1))]).astype(np.int64)
+        soff = torch.from_numpy(seg_off).to(dev, non_blocking=True)
+        total = int(seg_off[-1])
+        points = torch.empty((total, ps), dtype=torch.float32, device=dev)
+        seg = torch.empty((total,), dtype=torch.int64, device=dev)
+        _native.check(L.fcn_frustum_sunrgbd_label_fill(*args, gt.data_ptr(), soff.data_ptr(), points.data_ptr(), seg.data_ptr(),
+                                                       _native.current_stream(dev)), "fcn_frustum_sunrgbd_label_fill")
+        idx = torch.from_numpy(kept).to(dev, non_blocking=True)
+        starts = soff[::S][:D].index_select(0, idx).contiguous()
+        cnt = both[0].sum(1, dtype=torch.int32).index_select(0, idx).contiguous()
+        pos = both[1].sum(1, dtype=torch.int32).index_select(0, idx).contiguous()
+        if any(sub[d] is not None for d in kept):
+            # the positives the subsamples keep: one launch over the pre-kept boxes, one read of their counts
+            lens = [0 if sub[d] is None else len(sub[d]) for d in kept]
+            sub_off = torch.from_numpy(np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)).to(dev, non_blocking=True)
+            flat = torch.from_numpy(np.concatenate([sub[d] for d in kept if sub[d] is not None]).astype(np.int32)).to(dev, non_blocking=True)
+            pos = torch.zeros((len(kept),), dtype=torch.int32, device=dev)
+            _native.check(L.fcn_frustum_subset_pos(seg.data_ptr(), starts.data_ptr(), cnt.data_ptr(), flat.data_ptr(),
+                                                   sub_off.data_ptr(), len(kept), pos.data_ptr(), _native.current_stream(dev)),
+                          "fcn_frustum_subset_pos")
+            ok = pos.cpu().numpy() >= min_positives
+            if not ok.all():
+                kept = kept[ok]
+                if len(kept) == 0:
+                    return {"kept": kept}
+                okd = torch.from_numpy(np.nonzero(ok)[0]).to(dev, non_blocking=True)
+                idx, starts, cnt, pos = (x.index_select(0, okd).contiguous() for x in (idx, starts, cnt, pos))
+    pick = lambda x: x.index_select(0, idx).contiguous()
+    size = gt[:, 3:6] * 2.0                                                 # box3d_size = 2l, 2w, 2h (:217)
+    return {"points": points, "seg": seg, "off": torch.cat([starts, soff[-1:]]), "box2d": pick(boxes.float().double()),
+            "frustum_angle": pick(angle), "box3d": pick(corners), "heading": pick(gt[:, 6]), "size": pick(size),
+            "box_frame": pick(bframe), "cnt": cnt, "pos": pos, "kept": kept, "counts": counts[kept], "sub": [sub[d] for d in kept]}

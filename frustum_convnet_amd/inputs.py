@@ -306,6 +306,131 @@ class SunrgbdInputBuilder:
         return out
 
 
+    def _compose(self, choice, sub):
+        """The builder's draw through the reference's frustum subsample: choice (B,N) indexes the subsampled record where a box
+        has one, sub[b][choice[b]] the box's slice of the full packed selection."""
+        choice = np.array(choice, dtype=np.int32)
+        for b, ix in enumerate(sub):
+            if ix is not None:
+                choice[b] = np.asarray(ix, dtype=np.int32)[choice[b]]
+        return choice
+
+    def _calib_rows(self, K, Rtilt, box_frame):
+        dev = self.device
+        idx = box_frame.to(torch.int64)
+        gather = lambda m: torch.as_tensor(m).to(device=dev, dtype=torch.float64).reshape(-1, 9).index_select(0, idx).contiguous()
+        return gather(K), gather(Rtilt)
+
+    def build_device(self, sel, K, Rtilt, types, prob, draws=None, point_threshold=5):
+        """The five-scale model's inference batch (the reference's from_rgb_detection dict, provider_sample_sunrgbd.py:165-186:
+        point_cloud, rot_angle, rgb_prob, center_ref1..5, one_hot) straight from the device tensors of frustum.sunrgbd_candidates:
+        no point leaves the device.  sel: its dict; K, Rtilt (F,3,3): the frames' calibration, gathered per box through
+        sel["box_frame"]; types / prob: the class name and the 2-D detector's score of each of the D boxes; draws: (choice (B,N)
+        int32, ...) for the B surviving boxes -- indices into each box's RECORD, i.e. into its subsample where sel["sub"] has one
+        -- or None to draw like draw_sunrgbd from the records' row counts (no flip, no shift: inference).
+        A box whose record has fewer than point_threshold rows is skipped (sunrgbd/prepare_data.py:352); 'kept' (B,) int64 (host)
+        lists the survivors' box indices.  ONE launch of fcn_prepare_inputs_sunrgbd_infer, which gathers from the full packed
+        selection through sub[choice].  With no survivor the dict holds 'kept' alone."""
+        from .frustum import subsampled_counts
+        if self.device.type != "cuda":
+            raise RuntimeError("frustum_convnet_amd: input construction is a HIP kernel (MI355X only); no CPU fallback")
+        D, N = len(sel["counts"]), self.npoints
+        if len(types) != D or len(prob) != D:
+            raise ValueError("build_device: %d boxes, %d types, %d prob" % (D, len(types), len(prob)))
+        rows = subsampled_counts(sel["counts"], sel["sub"])
+        kept = np.nonzero(rows >= max(1, int(point_threshold)))[0]
+        B = len(kept)
+        if B == 0:
+            return {"kept": kept}
+        if draws is None:
+            draws = draw_sunrgbd(rows[kept], N, False, False)
+        dev = self.device
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev, non_blocking=True)
+        idx = up(kept)
+        pick = lambda x: x.index_select(0, idx).contiguous()
+        Kd, Rd = self._calib_rows(K, Rtilt, pick(sel["box_frame"]))
+        t = {"raw": sel["points"], "choice": up(self._compose(draws[0], [sel["sub"][d] for d in kept])),
+             "off": pick(sel["off"]),                                         # the kernel reads a sample's first row only
+             "fangle": pick(sel["frustum_angle"]), "box2d": pick(sel["box2d"]), "K": Kd, "R": Rd}
+        f32 = dict(dtype=torch.float32, device=dev)
+        out = {"point_cloud": torch.empty((B, 3, N), **f32), "rot_angle": torch.empty((B, 1), **f32)}
+        for s in range(5):
+            out["center_ref%d" % (s + 1)] = torch.empty((B, 3, self.L[s]), **f32)
+        desc = Inp5Desc(B, N, int(sel["points"].shape[1]), (ctypes.c_int32 * 5)(*self.L), (ctypes.c_double * 5)(*self.strides),
+                        self.max_depth, 0, 0)
+        refs = (ctypes.c_void_p * 5)(*[out["center_ref%d" % (s + 1)].data_ptr() for s in range(5)])
+        p = lambda x: x.data_ptr()
+        with torch.cuda.device(dev):
+            _native.check(_native.lib().fcn_prepare_inputs_sunrgbd_infer(
+                ctypes.byref(desc), p(t["raw"]), p(t["off"]), p(t["choice"]), p(t["fangle"]), p(t["box2d"]), p(t["K"]), p(t["R"]),
+                p(out["point_cloud"]), refs, p(out["rot_angle"]), _native.current_stream(dev)), "fcn_prepare_inputs_sunrgbd_infer")
+        for v in t.values():
+            v.record_stream(torch.cuda.current_stream(dev))
+        out["rgb_prob"] = up(np.asarray(prob, dtype=np.float32)[kept].reshape(B, 1))
+        if self.one_hot:
+            oh = np.zeros((B, len(self.classes)), dtype=np.float32)
+            oh[np.arange(B), [self.classes.index(types[i]) for i in kept]] = 1.0
+            out["one_hot"] = up(oh)
+        out["kept"] = kept
+        return out
+
+    def build_device_train(self, sel, K, Rtilt, types, draws=None, with_seg=True):
+        """The five-scale model's TRAINING batch -- the dict of build(), same keys, shapes and dtypes -- straight from the device
+        tensors of frustum.sunrgbd_training_candidates: no point, label or corner leaves the device.  sel: its dict; K, Rtilt
+        (F,3,3), gathered per box through sel["box_frame"]; types: the class name of each of the D boxes
+        sunrgbd_training_candidates was given (the kept ones are looked up through sel["kept"]); draws: (choice (K,N) int32, coin,
+        normal, hshift) for the K kept boxes -- choice indexes each box's RECORD, i.e. its subsample where sel["sub"] has one -- or
+        None to draw like the reference from the records' row counts.  ONE launch of fcn_prepare_inputs_sunrgbd, which gathers
+        points and labels from the full packed selection through sub[choice].  With no kept box the dict holds 'kept' alone."""
+        from .frustum import subsampled_counts
+        if self.device.type != "cuda":
+            raise RuntimeError("frustum_convnet_amd: input construction is a HIP kernel (MI355X only); no CPU fallback")
+        kept = np.asarray(sel["kept"], dtype=np.int64)
+        B, N = len(kept), self.npoints
+        if B == 0:
+            return {"kept": kept}
+        if draws is None:
+            draws = draw_sunrgbd(subsampled_counts(sel["counts"], sel["sub"]), N, self.random_flip, self.random_shift)
+        choice, coin, normal, hshift = draws
+        dev = self.device
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev, non_blocking=True)
+        Kd, Rd = self._calib_rows(K, Rtilt, sel["box_frame"])
+        t = {"raw": sel["points"], "off": sel["off"], "choice": up(self._compose(choice, sel["sub"])), "fangle": sel["frustum_angle"],
+             "box2d": sel["box2d"], "K": Kd, "R": Rd, "corners": sel["box3d"].reshape(B, 24), "heading": sel["heading"],
+             "size": sel["size"], "coin": up(np.asarray(coin, dtype=np.float64)), "normal": up(np.asarray(normal, dtype=np.float64)),
+             "hshift": up(np.asarray(hshift, dtype=np.float64))}
+        seg_raw = sel["seg"] if with_seg else None
+        f32 = dict(dtype=torch.float32, device=dev)
+        out = {"point_cloud": torch.empty((B, 3, N), **f32), "rot_angle": torch.empty((B, 1), **f32),
+               "cls_label": torch.empty((B, self.L[1]), dtype=torch.int64, device=dev),
+               "box3d_center": torch.empty((B, 3), **f32), "box3d_heading": torch.empty((B, 1), **f32),
+               "box3d_size": torch.empty((B, 3), **f32)}
+        for s in range(5):
+            out["center_ref%d" % (s + 1)] = torch.empty((B, 3, self.L[s]), **f32)
+        if with_seg:
+            out["seg_label"] = torch.empty((B, N), dtype=torch.int64, device=dev)
+        desc = Inp5Desc(B, N, int(sel["points"].shape[1]), (ctypes.c_int32 * 5)(*self.L), (ctypes.c_double * 5)(*self.strides),
+                        self.max_depth, 1 if self.random_flip else 0, 1 if self.random_shift else 0)
+        refs = (ctypes.c_void_p * 5)(*[out["center_ref%d" % (s + 1)].data_ptr() for s in range(5)])
+        p = lambda x: None if x is None else x.data_ptr()
+        with torch.cuda.device(dev):
+            _native.check(_native.lib().fcn_prepare_inputs_sunrgbd(
+                ctypes.byref(desc), p(t["raw"]), p(t["off"]), p(seg_raw), p(t["choice"]), p(t["fangle"]), p(t["box2d"]),
+                p(t["K"]), p(t["R"]), p(t["corners"]), p(t["heading"]), p(t["size"]), p(t["coin"]), p(t["normal"]),
+                p(t["hshift"]), p(out["point_cloud"]), refs, p(out["cls_label"]), p(out["box3d_center"]),
+                p(out["box3d_heading"]), p(out["box3d_size"]), p(out["rot_angle"]), p(out.get("seg_label")),
+                _native.current_stream(dev)), "fcn_prepare_inputs_sunrgbd")
+        for v in list(t.values()) + ([seg_raw] if with_seg else []):
+            v.record_stream(torch.cuda.current_stream(dev))
+        size_class = [self.classes.index(types[i]) for i in kept]
+        out["size_class"] = torch.tensor(size_class, dtype=torch.int64).view(B, 1).to(dev, non_blocking=True)
+        if self.one_hot:
+            oh = np.zeros((B, len(self.classes)), dtype=np.float32)
+            oh[np.arange(B), size_class] = 1.0
+            out["one_hot"] = up(oh)
+        return out
+
+
 def sunrgbd_records_from_fixture(g):
     """tests/golden/inputs_sunrgbd_b6.npz (make_golden_inputs_sunrgbd.py) as a list of records."""
     offs = np.concatenate([[0], np.cumsum(g["raw_counts"])])

@@ -527,6 +527,12 @@ int fcn_prepare_inputs_sunrgbd(const fcn_inp5_desc *d, const float *raw_pts, con
                                const double *coin, const double *normal, const double *hshift, float *point_cloud,
                                float *const center_ref[5], int64_t *cls_label, float *box3d_center, float *box3d_heading,
                                float *box3d_size, float *rot_angle, int64_t *seg_label, void *stream);
+/* Inference records of the SUN-RGBD loader (provider_sample_sunrgbd.py:165-186, from_rgb_detection): no label box in, no labels
+ * out, no flip and no shift -- point_cloud, center_ref[5] and rot_angle alone.  The same kernel without a label box, as
+ * fcn_prepare_inputs_infer is to fcn_prepare_inputs.  d->random_flip / random_shift must be 0. */
+int fcn_prepare_inputs_sunrgbd_infer(const fcn_inp5_desc *d, const float *raw_pts, const int64_t *pt_off, const int32_t *choice,
+                                     const double *frustum_angle, const double *box2d, const double *K, const double *Rtilt,
+                                     float *point_cloud, float *const center_ref[5], float *rot_angle, void *stream);
 
 /* Refinement-stage variant (cfgs/refine_car.yaml; datasets/provider_sample_refine.py::ProviderDataset.__getitem__ :176-315,
  * generate_ref :336-386, generate_labels :317-334, collate_fn :388-419): the sample is normalised to the first-stage
@@ -648,6 +654,53 @@ int fcn_frustum_label_fill(const float *frame_pts, const int64_t *frame_off, int
                            const double *V2C, const double *R0, const double *img_wh, const double *boxes,
                            const int32_t *box_frame, int D, int S, int clip_boxes, double clip_distance, const double *gt_box3d,
                            const int64_t *seg_off, float *out_pts, int64_t *out_seg, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * The SUN-RGBD front: upright-depth frames + per-frame K and Rtilt + 2-D boxes (+ one label 3-D box beside each) -> the raw
+ * records fcn_prepare_inputs_sunrgbd(_infer) takes.  Replaces the host loops of sunrgbd/prepare_data.py::extract_frustum_data
+ * (:132-267) and extract_frustum_data_from_rgb_detection (:270-381).  The grid, the segments (fcn_frustum_select_seg() rows), the
+ * two-call protocol (count, the caller's cumulative sum over the flattened (D*S) counts, fill), seg_off's bounding of every store
+ * and the refusals are those of fcn_frustum_select_count / _fill and fcn_frustum_label_count / _fill; only the geometry differs.
+ *   frame_pts (sum m_f, pt_stride >= 3) float32 UPRIGHT DEPTH x, y, z then r, g, b, ...; K (F,9), Rtilt (F,9) fp64 row-major;
+ *   boxes (D,4) xmin ymin xmax ymax, used as given (neither reference path clips); box_frame (D).
+ * Selected (one predicate, fp64 from the fp32 row, sums left to right): d = Rtilt^T . (x,y,z), c = (d0, -d2, d1), i = K . c,
+ * u = i0 / i2, v = i1 / i2; xmin <= u < xmax and ymin <= v < ymax.  There is no image-bounds test, no clip distance and no guard
+ * on i2 (the reference has none: a row behind the camera that projects into the box is selected there too).  A row with a
+ * non-finite x, y or z is never selected.  A selected row is stored in upright CAMERA coordinates, (x, -z, y) of the input row --
+ * an exact swap and negation -- followed by bit-exact copies of columns 3..pt_stride-1.
+ * frustum_angle (D) = -atan2(ud1, ud0) with X = ((cu - K02) * 20) / K00, Y = ((cv - K12) * 20) / K11, ud = Rtilt . (X, 20, -Y)
+ * for the box centre (cu, cv): project_image_to_upright_camera of (cu, cv, 20).
+ * Labelled pair: gt_box3d (D,7) fp64 = cx, cy, cz, l, w, h, heading in upright depth, l w h the HALF extents of the label file
+ * (SUNObject3d.l / .w / .h), heading = SUNObject3d.heading_angle.  seg_pos (D,S) counts the selected rows inside the box, out_seg
+ * is 1 for such a row; inside (closed, on the INPUT row): c = cos(-heading), s = sin(-heading), dx = x - cx, dy = y - cy,
+ * dz = z - cz, ax = c * dx + s * dy, ay = -s * dx + c * dy; |ax| <= l, |ay| <= w and |dz| <= h.  corners (D,8,3) =
+ * rotz(-heading) . (x_k, y_k, z_k) + centroid with x_k = -l l l -l (twice), y_k = w w -w -w (twice), z_k = h (four times) then -h
+ * (sunrgbd_utils.compute_box_3d's order), flipped to upright camera (X, -Z, Y): what fcn_prepare_inputs_sunrgbd takes as
+ * box3d_corners (heading = heading, size = 2l, 2w, 2h).
+ * D == 0: returns 0, touches nothing.  F == 0: returns 0 (the counts zero seg_cnt / seg_pos).  NULL pointers, pt_stride < 3,
+ * S < 1, D > 65535 and a frame longer than S * seg rows are FCN_E_BADARG with no launch; a box whose frame is out of range is
+ * never dereferenced -- its counts are 0, nothing else of it is written, the other boxes are processed and the call returns
+ * FCN_E_BADARG.  Every call synchronises the stream (box_frame and frame_off are read back first). */
+int fcn_frustum_sunrgbd_count(const float *frame_pts, const int64_t *frame_off, int F, int pt_stride, const double *K,
+                              const double *Rtilt, const double *boxes, const int32_t *box_frame, int D, int S,
+                              double *frustum_angle, int32_t *seg_cnt, void *stream);
+int fcn_frustum_sunrgbd_fill(const float *frame_pts, const int64_t *frame_off, int F, int pt_stride, const double *K,
+                             const double *Rtilt, const double *boxes, const int32_t *box_frame, int D, int S,
+                             const int64_t *seg_off, float *out_pts, void *stream);
+int fcn_frustum_sunrgbd_label_count(const float *frame_pts, const int64_t *frame_off, int F, int pt_stride, const double *K,
+                                    const double *Rtilt, const double *boxes, const int32_t *box_frame, int D, int S,
+                                    const double *gt_box3d, double *frustum_angle, int32_t *seg_cnt, int32_t *seg_pos,
+                                    double *corners, void *stream);
+int fcn_frustum_sunrgbd_label_fill(const float *frame_pts, const int64_t *frame_off, int F, int pt_stride, const double *K,
+                                   const double *Rtilt, const double *boxes, const int32_t *box_frame, int D, int S,
+                                   const double *gt_box3d, const int64_t *seg_off, float *out_pts, int64_t *out_seg, void *stream);
+/* The positives a unit keeps under a subsample of its rows (prepare_data.py:219-226 rejects on the count AFTER its 2048-row
+ * subsample): pos[u] = the number of j in [sub_off[u], sub_off[u+1]) with seg[off[u] + sub[j]] != 0; a unit whose range is empty
+ * has no subsample and counts all its cnt[u] rows.  seg int64 (out_seg), off (U) int64 first rows, cnt (U) int32, sub int32,
+ * sub_off (U+1) int64, pos (U) int32.  One workgroup per unit.  An index outside [0, cnt[u]) is skipped, never dereferenced.
+ * U == 0: returns 0, touches nothing. */
+int fcn_frustum_subset_pos(const int64_t *seg, const int64_t *off, const int32_t *cnt, const int32_t *sub, const int64_t *sub_off,
+                           int U, int32_t *pos, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * The cascade link for TRAINING the refinement stage: first-stage detections + the frames' label boxes -> the labelled raw
