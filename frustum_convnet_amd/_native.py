@@ -85,7 +85,8 @@ EXPORTS = ("fcn_arch", "fcn_build_hash", "fcn_stat_replicas", "fcn_query_depth_p
            "fcn_pn_pack_weights", "fcn_pn_pack_weights_all", "fcn_pn_infer_fold", "fcn_pn_infer", "fcn_pn_forward", "fcn_pn_backward", "fcn_pn_backward2", "fcn_pn_backward3", "fcn_pn_backward_dense", "fcn_pn_conv_fwd", "fcn_det_loss_tail", "fcn_det_loss_tail_rows", "fcn_det_loss_tail_rows2", "fcn_det_iou_metrics",
            "fcn_det_loss_tail_scratch_floats", "fcn_adam_step_f32", "fcn_sgd_step_f32", "fcn_adam_step_slots", "fcn_prepare_inputs", "fcn_prepare_inputs_refine", "fcn_prepare_inputs_sunrgbd", "fcn_refine_select_count", "fcn_refine_select_fill", "fcn_prepare_inputs_infer", "fcn_frustum_select_seg", "fcn_frustum_select_count", "fcn_frustum_select_fill", "fcn_frustum_label_count", "fcn_frustum_label_fill", "fcn_frustum_sunrgbd_count", "fcn_frustum_sunrgbd_fill", "fcn_frustum_sunrgbd_label_count", "fcn_frustum_sunrgbd_label_fill", "fcn_frustum_subset_pos", "fcn_prepare_inputs_sunrgbd_infer", "fcn_refine_match", "fcn_refine_label_count", "fcn_refine_label_fill", "fcn_stamp", "fcn_stream_capture_id",
            "fcn_convnet_sizes", "fcn_convnet_logits_ld", "fcn_convnet_pack", "fcn_convnet_forward", "fcn_convnet_forward2",
-           "fcn_convnet_backward", "fcn_box3d_iou_pair_f32", "fcn_decode_detections", "fcn_rotate_nms_3d")
+           "fcn_convnet_backward", "fcn_box3d_iou_pair_f32", "fcn_decode_detections", "fcn_rotate_nms_3d",
+           "fcn_decode_detections_rule", "fcn_box3d_corners", "fcn_det_match", "fcn_det_ap")
 
 _lib = None
 
@@ -251,6 +252,14 @@ def lib():
     L.fcn_box3d_iou_pair_f32.argtypes = [c_fp, c_fp, ctypes.c_int, c_fp, c_fp]
     L.fcn_decode_detections.restype = ctypes.c_int
     L.fcn_decode_detections.argtypes = [c_fp, ctypes.c_int] + [c_fp] * 5 + [ctypes.c_int] * 5 + [c_fp] * 3
+    L.fcn_decode_detections_rule.restype = ctypes.c_int
+    L.fcn_decode_detections_rule.argtypes = [c_fp, ctypes.c_int] + [c_fp] * 5 + [ctypes.c_int] * 6 + [c_fp] * 3
+    L.fcn_box3d_corners.restype = ctypes.c_int
+    L.fcn_box3d_corners.argtypes = [c_fp, ctypes.c_int, c_fp, ctypes.c_int, c_fp, c_fp]
+    L.fcn_det_match.restype = ctypes.c_int
+    L.fcn_det_match.argtypes = [c_fp, c_fp, ctypes.c_int, c_fp, c_fp, ctypes.c_int, c_fp, ctypes.c_int, ctypes.c_float] + [c_fp] * 4
+    L.fcn_det_ap.restype = ctypes.c_int
+    L.fcn_det_ap.argtypes = [c_fp] * 3 + [ctypes.c_int, c_fp, ctypes.c_int] + [c_fp] * 5
     L.fcn_rotate_nms_3d.restype = ctypes.c_int
     L.fcn_rotate_nms_3d.argtypes = [c_fp] * 3 + [ctypes.c_int] * 3 + [ctypes.c_float, ctypes.c_int] + [c_fp] * 3
     _lib = L

@@ -5,12 +5,16 @@
 //   decode_kernel       the per-frustum numpy loop of train/test_net_det.py:254-293: foreground selection (p_bg < p_fg, or the
 //                       arg-max of p_fg when a frustum has none / cfg.TEST.METHOD == 'top'), arg-max heading bin / size
 //                       cluster decode (models/box_transform.py:28-41,5-12), from_prediction_to_label_format
-//                       (datasets/provider_sample.py:375-387), the h/w/l >= 0.01 filter and the score p_fg + rgb_prob
+//                       (datasets/provider_sample.py:375-387), the h/w/l >= 0.01 filter and the score p_fg + rgb_prob.
+//                       Instantiated a second time for the SUN-RGBD loop (train/test_net_det_sunrgbd.py:208-252): p_fg > 0.5,
+//                       the box CENTRE (datasets/provider_sample_sunrgbd.py:374-385), score rgb_prob + max softmax(size scores)
 //   nms_kernel          rotate_nms_3d_cc (ops/pybind11/rbbox_iou.py:294-311) -> rotate_non_max_suppression_3d_cpu
 //                       (ops/pybind11/nms_cpu.h:148-240): per (frame, class) group, greedy in descending score order,
 //                       suppress when the rotated 3-D IoU >= thresh, keep the first top_k
 // The reference leaves the device for all three (numpy loops + boost::geometry polygon clipping on the host); here the
 // detections never leave HBM until the final keep lists are read.  The clip core is box_iou.h.
+// The SUN-RGBD evaluation behind the NMS (corners of the kept rows, matching to the label boxes, AP per class) is det_eval.h,
+// included at the end of this file.
 #include "fcn_common.h"
 #define FCN_HD __device__ __forceinline__
 #include "box_iou.h"
@@ -141,9 +145,7 @@ extern "C" int fcn_det_iou_metrics(const float *logits, int ld, const int64_t *c
 }
 
 // ------------------------------------------------------------------------------------------------
-#define DEC_T 256
-#define DEC_NB_MAX 16
-#define DEC_NS_MAX 8
+#define DEC_T 256            // (the bins and clusters of a row are walked in loops: no bound on either beyond ld)
 
 struct DecodeArgs {
     const float *logits;       // (B*L2, ld) rows: cols 0..1 cls, 2.. reg (3 centre, nb heading scores, nb residuals, ns size scores, 3*ns)
@@ -157,6 +159,9 @@ struct DecodeArgs {
     int B, L2, ld, nb, ns, method;
 };
 
+// RULE: FCN_DECODE_KITTI / FCN_DECODE_SUNRGBD.  The two differ in three places only (selection, ty, score); everything else is
+// one text, so the KITTI instantiation is the kernel it always was.
+template <int RULE>
 __global__ __launch_bounds__(DEC_T) void decode_kernel(DecodeArgs a)
 {
     __shared__ float best_s[DEC_T];
@@ -174,7 +179,7 @@ __global__ __launch_bounds__(DEC_T) void decode_kernel(DecodeArgs a)
         const float c0 = row[0], c1 = row[1];
         const float m = fmaxf(c0, c1), e0 = expf(c0 - m), e1 = expf(c1 - m);
         const float p0 = e0 / (e0 + e1), p1 = e1 / (e0 + e1);
-        cnt += (p0 < p1) ? 1 : 0;
+        cnt += (RULE == FCN_DECODE_SUNRGBD ? (p1 > 0.5f) : (p0 < p1)) ? 1 : 0;
         if (p1 > bs) { bs = p1; bi = l; }
     }
     best_s[tid] = bs;
@@ -204,7 +209,7 @@ __global__ __launch_bounds__(DEC_T) void decode_kernel(DecodeArgs a)
         const float c0 = row[0], c1 = row[1];
         const float m = fmaxf(c0, c1), e0 = expf(c0 - m), e1 = expf(c1 - m);
         const float p0 = e0 / (e0 + e1), p1 = e1 / (e0 + e1);
-        const bool sel = use_top ? (l == top) : (p0 < p1);
+        const bool sel = use_top ? (l == top) : (RULE == FCN_DECODE_SUNRGBD ? (p1 > 0.5f) : (p0 < p1));
         const float *o = row + 2;
         int ah = 0, as = 0;
         float mx = o[3];
@@ -225,11 +230,44 @@ __global__ __launch_bounds__(DEC_T) void decode_kernel(DecodeArgs a)
         // from_prediction_to_label_format: rotate_pc_along_y(centre, -rot) (+ ref_center), bottom centre, ry = heading + rot
         const float tx = cr * cx - sr * cz + rcx;
         const float tz = sr * cx + cr * cz + rcz;
-        const float ty = cy + rcy + 0.5f * sh;
+        float ty, score;
+        if constexpr (RULE == FCN_DECODE_SUNRGBD) {
+            // the centre stays the centre; score = rgb_prob + the largest softmax probability of the size scores
+            // (= 1 / sum_j exp(s_j - max), mx is that max here); the class probability is not in it
+            float den = 0.f;
+            for (int j = 0; j < ns; ++j) den += expf(ss[j] - mx);
+            ty = cy + rcy;
+            score = rgb + 1.f / den;
+        } else {
+            ty = cy + rcy + 0.5f * sh;
+            score = p1 + rgb;
+        }
         float *d = a.dets + r * 8;
-        d[0] = tx; d[1] = ty; d[2] = tz; d[3] = sl; d[4] = sw; d[5] = sh; d[6] = ang + rot; d[7] = p1 + rgb;
+        d[0] = tx; d[1] = ty; d[2] = tz; d[3] = sl; d[4] = sw; d[5] = sh; d[6] = ang + rot; d[7] = score;
         a.valid[r] = (sel && !(sh < 0.01f || sw < 0.01f || sl < 0.01f)) ? 1 : 0;
     }
+}
+
+extern "C" int fcn_decode_detections_rule(const float *logits, int ld, const float *center_ref2, const float *mean_size,
+                                          const float *rot_angle, const float *ref_center, const float *rgb_prob, int B, int L2,
+                                          int num_heading_bin, int num_size_cluster, int method, int rule, float *dets,
+                                          int32_t *valid, void *stream)
+{
+    if (!logits || !center_ref2 || !mean_size || !rot_angle || !dets || !valid) return FCN_E_BADARG;
+    if (B <= 0 || L2 <= 0 || num_heading_bin < 1 || num_size_cluster < 1) return FCN_E_BADARG;
+    if (ld < 2 + 3 + 2 * num_heading_bin + 4 * num_size_cluster) return FCN_E_BADARG;
+    if (method != 0 && method != 1) return FCN_E_BADARG;
+    if (rule != FCN_DECODE_KITTI && rule != FCN_DECODE_SUNRGBD) return FCN_E_BADARG;
+    DecodeArgs a;
+    a.logits = logits; a.ref2 = center_ref2; a.mean_size = mean_size; a.rot_angle = rot_angle; a.ref_center = ref_center;
+    a.rgb_prob = rgb_prob; a.dets = dets; a.valid = valid; a.B = B; a.L2 = L2; a.ld = ld; a.nb = num_heading_bin;
+    a.ns = num_size_cluster; a.method = method;
+    if (rule == FCN_DECODE_SUNRGBD)
+        hipLaunchKernelGGL(decode_kernel<FCN_DECODE_SUNRGBD>, dim3(B), dim3(DEC_T), 0, (hipStream_t)stream, a);
+    else
+        hipLaunchKernelGGL(decode_kernel<FCN_DECODE_KITTI>, dim3(B), dim3(DEC_T), 0, (hipStream_t)stream, a);
+    FCN_CHECK_LAUNCH();
+    return 0;
 }
 
 extern "C" int fcn_decode_detections(const float *logits, int ld, const float *center_ref2, const float *mean_size,
@@ -237,17 +275,8 @@ extern "C" int fcn_decode_detections(const float *logits, int ld, const float *c
                                      int num_heading_bin, int num_size_cluster, int method, float *dets, int32_t *valid,
                                      void *stream)
 {
-    if (!logits || !center_ref2 || !mean_size || !rot_angle || !dets || !valid) return FCN_E_BADARG;
-    if (B <= 0 || L2 <= 0 || num_heading_bin < 1 || num_size_cluster < 1) return FCN_E_BADARG;
-    if (ld < 2 + 3 + 2 * num_heading_bin + 4 * num_size_cluster) return FCN_E_BADARG;
-    if (method != 0 && method != 1) return FCN_E_BADARG;
-    DecodeArgs a;
-    a.logits = logits; a.ref2 = center_ref2; a.mean_size = mean_size; a.rot_angle = rot_angle; a.ref_center = ref_center;
-    a.rgb_prob = rgb_prob; a.dets = dets; a.valid = valid; a.B = B; a.L2 = L2; a.ld = ld; a.nb = num_heading_bin;
-    a.ns = num_size_cluster; a.method = method;
-    hipLaunchKernelGGL(decode_kernel, dim3(B), dim3(DEC_T), 0, (hipStream_t)stream, a);
-    FCN_CHECK_LAUNCH();
-    return 0;
+    return fcn_decode_detections_rule(logits, ld, center_ref2, mean_size, rot_angle, ref_center, rgb_prob, B, L2, num_heading_bin,
+                                      num_size_cluster, method, FCN_DECODE_KITTI, dets, valid, stream);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -395,3 +424,6 @@ extern "C" int fcn_rotate_nms_3d(const float *dets, const int32_t *valid, const 
     FCN_CHECK_LAUNCH();
     return 0;
 }
+
+// ------------------------------------------------------------------------------------------------
+#include "det_eval.h"

@@ -599,14 +599,18 @@ class PointNetDet(nn.Module):
         in some part (the step-loop machinery -- split backward, next-batch prefetch -- follows it)."""
         return torch.is_grad_enabled() and (self.training or self.feat_net.bn_frozen or getattr(self.conv_net, "bn_frozen", False))
 
-    def detect(self, data_dicts, unit_group=None, num_groups=None, method=None, thresh=None, top_k=300):
+    def detect(self, data_dicts, unit_group=None, num_groups=None, method=None, thresh=None, top_k=300, rule=None):
         """Inference tail on the device (train/test_net_det.py:193-293 + :126-152): eval forward, decode into label-format
         boxes, rotated 3-D NMS per (frame, class) group.  data_dicts may carry 'rot_angle' (B,1), 'ref_center' (B,3) and
         'rgb_prob' (B,1) as the reference's test loader does (:201-214 defaults: zeros / ones).  unit_group (B,) int32 maps
         each frustum to its (frame, class) group (default: every frustum its own group).
         Returns dets (B*L2, 8) [tx,ty,tz,l,w,h,ry,score], valid (B*L2,), keep (G, top_k), keep_cnt (G,) -- device tensors;
-        with method 'top' (cfg.TEST.METHOD default) there is one candidate per frustum and no suppression is run."""
+        with method 'top' (cfg.TEST.METHOD default) there is one candidate per frustum and no suppression is run.
+        rule: the decode rule of detect.decode_detections; None means "kitti" for EVERY model, the five-scale SUN-RGBD one
+        included -- "sunrgbd" (train/test_net_det_sunrgbd.py:208-252: p_fg > 0.5, box centre, score rgb_prob + max size
+        probability) is opt-in."""
         from . import detect as fdet
+        rule = "kitti" if rule is None else rule
         if self.training:
             raise RuntimeError("detect() runs in eval mode")
         method = cfg.TEST.METHOD if method is None else method
@@ -622,7 +626,7 @@ class PointNetDet(nn.Module):
         rot = data_dicts.get('rot_angle')
         rot = torch.zeros(B, device=dev) if rot is None else rot.to(dev)
         dets, valid = fdet.decode_detections(self.last_logits64, refs2, self._mean_size, rot, data_dicts.get('ref_center'),
-                                             data_dicts.get('rgb_prob'), self.num_bins, self.num_size_cluster, method)
+                                             data_dicts.get('rgb_prob'), self.num_bins, self.num_size_cluster, method, rule)
         if unit_group is None:
             unit_group = torch.arange(B, dtype=torch.int32, device=dev)
             num_groups = B

@@ -31,6 +31,9 @@
  *   fcn_box3d_iou_pair_f32      rbbox_iou_3d_pair, ops/pybind11/box_ops.h:173-260 (boost polygon clipping on the host)
  *   fcn_decode_detections       the numpy decode loop of train/test_net_det.py:254-293 + from_prediction_to_label_format
  *   fcn_rotate_nms_3d           rotate_nms_3d_cc, ops/pybind11/rbbox_iou.py:294-311 + nms_cpu.h:148-240
+ *   fcn_decode_detections_rule  the same loop with the SUN-RGBD rule of train/test_net_det_sunrgbd.py:208-252
+ *   fcn_box3d_corners           compute_box_3d, datasets/data_utils.py:44-70
+ *   fcn_det_match, fcn_det_ap   eval_det_cls + voc_ap, train/sunrgbd_eval/eval_det.py:41-72,89-169
  *   fcn_stamp                   (measurement aid, no reference counterpart)
  *   fcn_stream_capture_id       (graph-capture bookkeeping of the Python layer, no reference counterpart)
  *
@@ -458,6 +461,17 @@ int fcn_decode_detections(const float *logits, int ld, const float *center_ref2,
                           const float *rot_angle, const float *ref_center, const float *rgb_prob, int B, int L2,
                           int num_heading_bin, int num_size_cluster, int method, float *dets, int32_t *valid,
                           void *stream);
+/* The same with the decode rule as an argument.  FCN_DECODE_KITTI: the entry above, bit for bit.  FCN_DECODE_SUNRGBD: the loop of
+ * train/test_net_det_sunrgbd.py:208-252 -- method 1 selects every position with p_fg > 0.5 (the arg-max of p_fg when a frustum has
+ * none), the centre stays the box centre (datasets/provider_sample_sunrgbd.py:374-385: no h/2 shift of ty), and
+ * score = rgb_prob + max_j softmax(size scores)_j; the class probability is not part of the score.  Heading / size decode, the
+ * rotation by -rot_angle, ref_center, ry = heading + rot_angle and the h,w,l >= 0.01 filter are the same. */
+#define FCN_DECODE_KITTI 0
+#define FCN_DECODE_SUNRGBD 1
+int fcn_decode_detections_rule(const float *logits, int ld, const float *center_ref2, const float *mean_size,
+                               const float *rot_angle, const float *ref_center, const float *rgb_prob, int B, int L2,
+                               int num_heading_bin, int num_size_cluster, int method, int rule, float *dets, int32_t *valid,
+                               void *stream);
 /* rotate_nms_3d_cc (ops/pybind11/rbbox_iou.py:294-311) -> rotate_non_max_suppression_3d_cpu (ops/pybind11/nms_cpu.h:148-240)
  * for num_groups independent detection sets at once (one per (frame, class), train/test_net_det.py:126-152): dets rows are
  * organised in units of rows_per_unit consecutive rows (one frustum each), unit_group (num_units) in [0, num_groups) assigns
@@ -466,6 +480,35 @@ int fcn_decode_detections(const float *logits, int ld, const float *center_ref2,
  * holds more than 4096 candidates (FCN_E_LIMIT condition reported per group, the other groups are still processed). */
 int fcn_rotate_nms_3d(const float *dets, const int32_t *valid, const int32_t *unit_group, int num_units, int rows_per_unit,
                       int num_groups, float thresh, int top_k, int32_t *keep, int32_t *keep_cnt, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * SUN-RGBD evaluation behind the NMS (csrc/det_eval.h).  The reference turns every kept row into corners and scores them in
+ * Python on the host (train/test_net_det_sunrgbd.py:94-99, train/sunrgbd_eval/eval_det.py:89-169).
+ * ------------------------------------------------------------------------------------------- */
+/* compute_box_3d (datasets/data_utils.py:44-70) of n rows of dets (num_dets,8) = tx, ty, tz, l, w, h, ry, score with (tx,ty,tz)
+ * the box CENTRE: rows (n) int32 picks them (NULL: rows 0 .. n-1, n <= num_dets).  corners (n,8,3) float32, corner k at
+ * x = +-l/2 (+ + - - + + - -), y = +-h/2 (+ + + + - - - -), z = +-w/2 (+ - - + + - - +), rotated by roty(ry), moved to the centre.
+ * A row index outside [0, num_dets) (an unused keep slot) is never dereferenced: its 24 numbers are NaN. */
+int fcn_box3d_corners(const float *dets, int num_dets, const int32_t *rows, int n, float *corners, void *stream);
+/* The matching loop of eval_det_cls (eval_det.py:134-159) for G (image, class) groups at once, CSR: the detections of group g are
+ * rows [det_off[g], det_off[g+1]) of det_corners (nd,8,3) / scores (nd), its label boxes rows [gt_off[g], gt_off[g+1]) of
+ * gt_corners (ng,8,3); both offset arrays (G+1) int32 ON THE DEVICE, ascending from 0 to nd / ng (the caller checks them on the
+ * host; the kernel clamps what it reads to the buffers).  Corners in the order of compute_box_3d, as rbbox_iou_3d_pair reads
+ * them (BEV polygon 6,7,4,5; y extents from corners 0 and 4).
+ *   ovmax (nd): the largest 3-D IoU with a label box of the group (-inf when it has none); jmax (nd) int32: that label's index
+ *   INSIDE its group, the first maximum under strict > (-1 when the group has none); tp (nd) int32: 1 when ovmax > thresh and no
+ *   detection of the group with the same jmax and ovmax > thresh comes earlier in (score descending, input index ascending) --
+ *   the reference's greedy walk, in which a detection whose best label is taken is a false positive even when a second label
+ *   would qualify.  Equal scores: the lower input index first (np.argsort in the reference is unstable there). */
+int fcn_det_match(const int32_t *det_off, const int32_t *gt_off, int G, const float *det_corners, const float *scores, int nd,
+                  const float *gt_corners, int ng, float thresh, int32_t *tp, float *ovmax, int32_t *jmax, void *stream);
+/* Precision / recall and AP per class (eval_det.py:161-169 + voc_ap :41-72, use_07_metric=False) of nd detections with flags tp
+ * (nd) int32, scores (nd), det_class (nd) int32 in [0, C) and npos (C) int32 label boxes per class (every npos > 0: the caller's
+ * duty).  rank (nd) int32: the place of a detection inside its class by (score descending, input index ascending); rec / prec (nd)
+ * fp64: class c's curve in rank order at [base_c, base_c + n_c), base_c = number of detections of classes < c; ap (C) fp64, 0
+ * for a class without a detection.  Integer cumulative counts; the curve, the envelope and the sum in fp64. */
+int fcn_det_ap(const int32_t *tp, const float *scores, const int32_t *det_class, int nd, const int32_t *npos, int C,
+               int32_t *rank, double *rec, double *prec, double *ap, void *stream);
 
 /* Measurement aid: stores the device's constant-rate wall clock (100 MHz ticks) into *slot, in stream order. */
 int fcn_stamp(uint64_t *slot, void *stream);
