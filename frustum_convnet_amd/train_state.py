@@ -120,6 +120,18 @@ class FlatTrainState:
                 k = int(n[len("feat_net.pointnet"):].split(".")[0]) - 1
                 lo, hi = self.scale_ranges.get(k, (o, o))
                 self.scale_ranges[k] = (min(lo, o), max(hi, (o + p.numel() + 3) // 4 * 4))
+        # adam_step_scale(k) launches over [lo, hi) alone and advances the step counter of every STEP_SPAN tile it touches: a parameter
+        # of another scale -- or of none -- inside one of those tiles would have its counter advanced without being stepped (or be
+        # stepped twice per training step once its own launch follows).  The padding above keeps the scales apart; anything else
+        # that lands in a scale's tiles is refused here instead of training with a skewed bias correction
+        for k, (lo, hi) in self.scale_ranges.items():
+            tiles_end = (hi + STEP_SPAN - 1) // STEP_SPAN * STEP_SPAN
+            inside = lambda n: n.startswith("feat_net.pointnet%d." % (k + 1))
+            for n, p, o in zip(self.names, params, offs):
+                if inside(n) != (lo <= o and o + p.numel() <= hi) or (not inside(n) and o < tiles_end and o + p.numel() > lo):
+                    raise ValueError("FlatTrainState: parameter '%s' at [%d, %d) shares an optimiser tile (%d elements) with PointNet "
+                                     "scale %d at [%d, %d): per-scale steps would advance its step counter; register it before the "
+                                     "scales or outside feat_net" % (n, o, o + p.numel(), STEP_SPAN, k + 1, lo, hi))
         self._pending = {}          # name -> the torch.distributed work of an all-reduce started and not yet waited for
         if optimizer == "sgd":          # lr, momentum, weight_decay, grad_scale; the momentum buffer lives in exp_avg
             self.hyper = torch.tensor([lr, momentum, weight_decay, 1.0 / self.world, 0.0, 1.0 / self.world], device=dev,
@@ -229,10 +241,13 @@ class FlatTrainState:
 
     def adam_step_scale(self, k):
         """The optimiser step of PointNet scale k (0-based) alone, on the current stream: the slice feat_net.pointnet<k+1>.* of the
-        [pointnet] bucket.  A step loop that runs it right behind that scale's backward -- on the stream the scale's backward ran on --
-        lets the scale's NEXT forward follow without waiting for the other scales (round 6 built that step: bit-identical, 2.5 % slower
-        on MI355X, EXPERIMENTS 6.8 -- not in bench.py).  Every scale must then be stepped exactly once per training step and the
-        [pointnet] bucket not at all; world 1 only (the gradients are not reduced)."""
+        [pointnet] bucket.  Callable only after the COMPLETE backward: while a split backward is pending (phase 2 not, or only partly,
+        differentiated) _step_range refuses every range below the bucket cut, so a scale cannot be stepped right behind its own
+        backward while other scales are still to come.  What it buys is a per-scale dependency inside a captured step: the scale's
+        NEXT forward can follow its step without waiting for the other scales' steps (round 6 built that step: bit-identical, 2.5 %
+        slower on MI355X, EXPERIMENTS 6.8 -- not in bench.py).  Every scale must then be stepped exactly once per training step and
+        the [pointnet] bucket not at all; world 1 only (the gradients are not reduced).  The launch uses the step-counter slots of
+        the whole-buffer launch's workgroups over the same tiles (__init__ refuses a layout in which they hold anything else)."""
         if self.comm:
             raise RuntimeError("FlatTrainState.adam_step_scale: per-scale steps are for a world of one rank (no all-reduce in between)")
         lo, hi = self.scale_ranges[k]
@@ -330,7 +345,8 @@ class FlatTrainState:
                         self.exp_avg[o:o + n].zero_()
                     else:
                         self.exp_avg[o:o + n].copy_(st["momentum_buffer"].reshape(-1))
-                self._step_slots.fill_(int(sd.get("step", 0)))
+                self._step_slots.zero_()                 # (SGD keeps its step count in slot 0 alone, as _step_range does)
+                self._step_slots[0:1].fill_(int(sd.get("step", 0)))
                 self.hyper[0:3].copy_(torch.tensor([group["lr"], group["momentum"], group["weight_decay"]],
                                                    dtype=torch.float32))
             return

@@ -207,6 +207,24 @@ for _path in ("build", "build_infer", "build_device", "build_device_train"):
     CASES += [("test_gpu_inputs_edges", "test_a_sample_without_a_window_is_refused", (_path, (1.6, -0.3, 0.0), 1, "-0.3")),
               ("test_gpu_inputs_edges", "test_a_sample_without_a_window_is_refused", (_path, (1.6, 0.9, float("nan")), 2, "nan"))]
 
+# the optimiser entries and FlatTrainState on a toy module against the fp64 restatement (tests/optim_ref.py): every case of the
+# module but the captured-graph one (replay cannot be emulated)
+import optim_ref  # noqa: E402
+
+CASES += [("test_gpu_optim", "test_adam_entry_one_step_at_a_time", (n,)) for n in optim_ref.SIZES]
+CASES += [("test_gpu_optim", "test_sgd_entry_one_step_at_a_time", (n,)) for n in optim_ref.SIZES]
+CASES += [
+    ("test_gpu_optim", "test_adam_entry_refusals_touch_nothing", ()),
+    ("test_gpu_optim", "test_sgd_entry_refusals_touch_nothing", ()),
+    ("test_gpu_optim", "test_toy_layout", ()),
+    ("test_gpu_optim", "test_parameter_in_a_scale_tile_is_refused", ()),
+    ("test_gpu_optim", "test_toy_twins_whole_bucket_and_scale_steps", ("adam",)),
+    ("test_gpu_optim", "test_toy_twins_whole_bucket_and_scale_steps", ("sgd",)),
+    ("test_gpu_optim", "test_toy_world_of_eight_applies_one_eighth", ()),
+    ("test_gpu_optim", "test_toy_state_transfer", ("adam",)),
+    ("test_gpu_optim", "test_toy_state_transfer", ("sgd",)),
+]
+
 
 def _ident(c):
     a = c[2]
