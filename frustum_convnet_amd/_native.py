@@ -86,7 +86,8 @@ EXPORTS = ("fcn_arch", "fcn_build_hash", "fcn_stat_replicas", "fcn_query_depth_p
            "fcn_det_loss_tail_scratch_floats", "fcn_adam_step_f32", "fcn_sgd_step_f32", "fcn_adam_step_slots", "fcn_prepare_inputs", "fcn_prepare_inputs_refine", "fcn_prepare_inputs_sunrgbd", "fcn_refine_select_count", "fcn_refine_select_fill", "fcn_prepare_inputs_infer", "fcn_frustum_select_seg", "fcn_frustum_select_count", "fcn_frustum_select_fill", "fcn_frustum_label_count", "fcn_frustum_label_fill", "fcn_frustum_sunrgbd_count", "fcn_frustum_sunrgbd_fill", "fcn_frustum_sunrgbd_label_count", "fcn_frustum_sunrgbd_label_fill", "fcn_frustum_subset_pos", "fcn_prepare_inputs_sunrgbd_infer", "fcn_refine_match", "fcn_refine_label_count", "fcn_refine_label_fill", "fcn_stamp", "fcn_stream_capture_id",
            "fcn_convnet_sizes", "fcn_convnet_logits_ld", "fcn_convnet_pack", "fcn_convnet_forward", "fcn_convnet_forward2",
            "fcn_convnet_backward", "fcn_box3d_iou_pair_f32", "fcn_decode_detections", "fcn_rotate_nms_3d",
-           "fcn_decode_detections_rule", "fcn_box3d_corners", "fcn_det_match", "fcn_det_ap")
+           "fcn_decode_detections_rule", "fcn_box3d_corners", "fcn_det_match", "fcn_det_ap",
+           "fcn_kitti_label_rows", "fcn_kitti_overlaps", "fcn_kitti_pass_a", "fcn_kitti_thresholds", "fcn_kitti_pass_b", "fcn_kitti_curves")
 
 _lib = None
 
@@ -260,6 +261,20 @@ def lib():
     L.fcn_det_match.argtypes = [c_fp, c_fp, ctypes.c_int, c_fp, c_fp, ctypes.c_int, c_fp, ctypes.c_int, ctypes.c_float] + [c_fp] * 4
     L.fcn_det_ap.restype = ctypes.c_int
     L.fcn_det_ap.argtypes = [c_fp] * 3 + [ctypes.c_int, c_fp, ctypes.c_int] + [c_fp] * 5
+    if hasattr(L, "fcn_kitti_curves") or "FCN_LIB_NAME" not in os.environ:     # (A/B builds of older kernel sources lack them)
+        ks_in = [c_fp] * 3 + [ctypes.c_int, c_fp, c_fp, ctypes.c_int, c_fp, c_fp, ctypes.c_int, c_fp, ctypes.c_int]
+        L.fcn_kitti_label_rows.restype = ctypes.c_int
+        L.fcn_kitti_label_rows.argtypes = [c_fp, ctypes.c_int, c_fp, ctypes.c_int, c_fp, ctypes.c_int] + [c_fp] * 4
+        L.fcn_kitti_overlaps.restype = ctypes.c_int
+        L.fcn_kitti_overlaps.argtypes = ks_in + [c_fp] * 2
+        L.fcn_kitti_pass_a.restype = ctypes.c_int
+        L.fcn_kitti_pass_a.argtypes = ks_in + [ctypes.c_int] + [c_fp] * 5
+        L.fcn_kitti_thresholds.restype = ctypes.c_int
+        L.fcn_kitti_thresholds.argtypes = [c_fp] * 3 + [ctypes.c_int] + [c_fp] * 4
+        L.fcn_kitti_pass_b.restype = ctypes.c_int
+        L.fcn_kitti_pass_b.argtypes = ks_in + [ctypes.c_int] + [c_fp] * 6
+        L.fcn_kitti_curves.restype = ctypes.c_int
+        L.fcn_kitti_curves.argtypes = [c_fp] * 3 + [ctypes.c_int, c_fp, ctypes.c_int] + [c_fp] * 5
     L.fcn_rotate_nms_3d.restype = ctypes.c_int
     L.fcn_rotate_nms_3d.argtypes = [c_fp] * 3 + [ctypes.c_int] * 3 + [ctypes.c_float, ctypes.c_int] + [c_fp] * 3
     _lib = L

@@ -14,7 +14,8 @@
 // The reference leaves the device for all three (numpy loops + boost::geometry polygon clipping on the host); here the
 // detections never leave HBM until the final keep lists are read.  The clip core is box_iou.h.
 // The SUN-RGBD evaluation behind the NMS (corners of the kept rows, matching to the label boxes, AP per class) is det_eval.h,
-// included at the end of this file.
+// included at the end of this file, and behind it the KITTI evaluation (label rows, overlaps, the two passes of the official
+// protocol, thresholds, curves and AP), kitti_eval.h.
 #include "fcn_common.h"
 #define FCN_HD __device__ __forceinline__
 #include "box_iou.h"
@@ -427,3 +428,4 @@ extern "C" int fcn_rotate_nms_3d(const float *dets, const int32_t *valid, const 
 
 // ------------------------------------------------------------------------------------------------
 #include "det_eval.h"
+#include "kitti_eval.h"

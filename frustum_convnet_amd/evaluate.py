@@ -7,6 +7,9 @@ train/sunrgbd_eval/eval_det.py:89-169 (eval_det_cls + voc_ap) clips every detect
 class in Python, matches greedily in descending score and sums the precision / recall curve to an AP per class.  Here no point,
 logit, box or IoU crosses to the host: the keep lists are read between the NMS and the corners (they size the buffers), and the
 result is a dict of device tensors -- the AP table is what a caller reads.  No CPU fallback: CPU tensors raise.
+
+KITTI detections and labels to AP per class, difficulty and metric (C-ABI fcn_kitti_*; csrc/kitti_eval.h): kitti_label_rows,
+kitti_eval, kitti_results below -- the reference's train/test_net_det.py:88-123 + train/kitti_eval/evaluate_object_3d_offline.cpp.
 """
 import numpy as np
 import torch
@@ -79,6 +82,171 @@ def match_detections_ap(det_corners, scores, det_off, gt_corners, gt_off, group_
     for t in (doff_d, goff_d, dcls, dc, sc, gc):
         t.record_stream(torch.cuda.current_stream(dev))
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# KITTI: detections and labels to AP per class, difficulty and metric (C-ABI fcn_kitti_*; csrc/kitti_eval.h).
+#
+# Reference: train/test_net_det.py:88-123 writes every kept row as a line of label-format text and
+# train/kitti_eval/evaluate_object_3d_offline.cpp ("the evaluator") reads the files back and clips every (detection, label) pair
+# with boost polygons once per class x difficulty x metric x (1 + thresholds).  Here a pair is clipped once in fp32 and the
+# detections never leave the device.  OUT OF SCOPE: the '%.4f' / '%f' text round trip of the result files (the evaluator sees
+# numbers rounded to 4 decimals, this code the float32 values), the gnuplot plots and the mail.
+KITTI_CLASSES = ("Car", "Pedestrian", "Cyclist")                                       # det_class 0, 1, 2
+KITTI_TYPES = ("Car", "Pedestrian", "Cyclist", "Van", "Person_sitting", "DontCare")    # gt_type 0 .. 5; anything else: 6
+KITTI_LISTS, KITTI_SLOTS = 27, 41
+
+
+def kitti_type_codes(names, table=KITTI_TYPES):
+    """Type names -> int codes: the place of each name in `table` (lower / upper case ignored, as the evaluator's strcasecmp does),
+    len(table) for a name that is not in it.  table=KITTI_TYPES: gt_type.  table=KITTI_CLASSES: det_class, where 3 -- like any value
+    outside 0..2 -- is a type that is not evaluated."""
+    low = [t.lower() for t in table]
+    return np.asarray([low.index(str(n).lower()) if str(n).lower() in low else len(table) for n in names], dtype=np.int32)
+
+
+def kitti_label_rows(dets, rows, boxes2d, row_box):
+    """The label-format row of every kept detection (train/test_net_det.py:88-105, :284-293): dets (R,8) [tx,ty,tz,l,w,h,ry,score]
+    as decode_detections(rule="kitti") writes them, rows (n) the kept rows (None: all), boxes2d (D,4) the 2-D boxes and row_box
+    (n) the box each kept row's frustum came from.  Device tensors in (rows / row_box may be host sequences), device tensors out:
+    table (n,13) float32 [alpha, x1,y1,x2,y2, h,w,l, tx,ty,tz, ry, score] with alpha = compute_alpha(tx, tz, ry)
+    (datasets/provider_sample.py:389-394) and ok (n) int32, 0 where h, w or l < 0.01 -- the reference drops such a row."""
+    who = "kitti_label_rows"
+    _need_cuda(dets, who)
+    d = dets.detach().contiguous().float()
+    if d.dim() != 2 or d.shape[1] != 8:
+        raise ValueError("%s: dets must be (R, 8), got %s" % (who, tuple(dets.shape)))
+    dev = d.device
+    b = torch.as_tensor(boxes2d).detach().to(device=dev, dtype=torch.float32).contiguous()
+    if b.dim() != 2 or b.shape[1] != 4:
+        raise ValueError("%s: boxes2d must be (D, 4), got %s" % (who, tuple(b.shape)))
+    r = None if rows is None else torch.as_tensor(rows).to(device=dev, dtype=torch.int32).contiguous().view(-1)
+    rb = torch.as_tensor(row_box).to(device=dev, dtype=torch.int32).contiguous().view(-1)
+    n = int(d.shape[0]) if r is None else int(r.numel())
+    if rb.numel() != n:
+        raise ValueError("%s: %d rows but %d row_box entries" % (who, n, rb.numel()))
+    table = torch.empty((n, 13), dtype=torch.float32, device=dev)
+    ok = torch.empty((n,), dtype=torch.int32, device=dev)
+    p = lambda t: t.data_ptr() if t is not None and t.numel() else None
+    with torch.cuda.device(dev):
+        _native.check(_native.lib().fcn_kitti_label_rows(p(d), int(d.shape[0]), p(r), n, p(b), int(b.shape[0]), p(rb), p(table), p(ok),
+                                                         _native.current_stream(dev)), "fcn_kitti_label_rows")
+    return table, ok
+
+
+def kitti_eval(det_table, det_class, det_off, gt_table, gt_type, gt_off, classes=(0, 1, 2)):
+    """The official KITTI evaluation of every class, difficulty and metric at once.  Detections and labels come per frame in CSR
+    form: det_table (nd,13) float32 on the device (kitti_label_rows' rows), det_class (nd) int codes over KITTI_CLASSES (anything
+    else: a type that is not evaluated), det_off (F+1); gt_table (ng,14) [truncation, occlusion, alpha, x1,y1,x2,y2, h,w,l,
+    tx,ty,tz, ry], gt_type (ng) int codes over KITTI_TYPES (6: any other type), gt_off (F+1) -- the offsets are host sequences.
+    classes: the classes to evaluate.
+    Returns a dict of device tensors, indexed [metric (image, ground, 3-D)][class][difficulty (easy, moderate, hard)]:
+    precision (3,3,3,41) float64, aos (3,3,41), ap (3,3,3), aos_ap (3,3); per list k = (metric * 3 + class) * 3 + difficulty:
+    thresholds (27,41) float64 with num_thresholds (27), n_gt (27), tp / fp / fn (27,41) int32; and overlaps (npairs,3) float32
+    (pair (d, g) of frame f at pair_off[f] + (d - det_off[f]) * labels_of_f + (g - gt_off[f]); pair_off: host int64), flags (10).
+    The evaluator's host-side rules: a class without a detection (x1 >= 0 / tx != -1000 / ty != -1000 for the three metrics) is
+    not evaluated, nor one left out of `classes` -- its precision / ap rows are NaN; aos / aos_ap are NaN throughout when any
+    detection's alpha equals -10.  0 / 0 (no true and no false positive at a threshold) is NaN as IEEE has it and the evaluator
+    prints it.  AP is summed in fp64 (the evaluator: in float, for printing only; 11 * 2^-24 * 100 < 7e-5 away)."""
+    who = "kitti_eval"
+    _need_cuda(det_table, who)
+    dev = det_table.device
+    dt = det_table.detach().to(dtype=torch.float32).contiguous()
+    if dt.dim() != 2 or dt.shape[1] != 13:
+        raise ValueError("%s: det_table must be (nd, 13), got %s" % (who, tuple(det_table.shape)))
+    gtab = torch.as_tensor(gt_table).detach().to(device=dev, dtype=torch.float32).contiguous()
+    if gtab.dim() != 2 or gtab.shape[1] != 14:
+        raise ValueError("%s: gt_table must be (ng, 14), got %s" % (who, tuple(gtab.shape)))
+    nd, ng = int(dt.shape[0]), int(gtab.shape[0])
+    dcl = torch.as_tensor(det_class).detach().to(device=dev, dtype=torch.int32).contiguous().view(-1)
+    gty = torch.as_tensor(gt_type).detach().to(device=dev, dtype=torch.int32).contiguous().view(-1)
+    if dcl.numel() != nd or gty.numel() != ng:
+        raise ValueError("%s: %d detections / %d classes, %d labels / %d types" % (who, nd, dcl.numel(), ng, gty.numel()))
+    doff, goff = _offsets(who, "det_off", det_off, nd), _offsets(who, "gt_off", gt_off, ng)
+    F = len(doff) - 1
+    if len(goff) != F + 1:
+        raise ValueError("%s: %d / %d offsets: detections and labels must count the same frames" % (who, len(doff), len(goff)))
+    cl = sorted(set(int(c) for c in classes))
+    if not cl or cl[0] < 0 or cl[-1] > 2:
+        raise ValueError("%s: classes must be a non-empty subset of (0, 1, 2), got %r" % (who, classes))
+    mask = sum(1 << c for c in cl)
+    poff = np.concatenate([[0], np.cumsum(np.diff(doff) * np.diff(goff))]).astype(np.int64)
+    npairs = int(poff[-1])
+    if npairs >= 2 ** 31:
+        raise ValueError("%s: %d (detection, label) pairs; the entry points index with int32" % (who, npairs))
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev, non_blocking=True)
+    doff_d, goff_d, poff_d = up(doff.astype(np.int32)), up(goff.astype(np.int32)), up(poff.astype(np.int32))
+    z = lambda shape, dtype: torch.zeros(shape, dtype=dtype, device=dev)
+    i32, f32, f64 = torch.int32, torch.float32, torch.float64
+    ov, flags = z((npairs, 3), f32), z((10,), i32)
+    assigned, tp_score, srt = z((KITTI_LISTS, nd, 2), i32), z((KITTI_LISTS, ng), f32), z((KITTI_LISTS, ng), f32)
+    tp_count, n_gt, nthr = z((KITTI_LISTS,), i32), z((KITTI_LISTS,), i32), z((KITTI_LISTS,), i32)
+    thr, counts, sim = z((KITTI_LISTS, KITTI_SLOTS), f64), z((3, KITTI_LISTS, KITTI_SLOTS), i32), z((F, 9, KITTI_SLOTS), f64)
+    prec, aos, ap, aos_ap = z((3, 3, 3, KITTI_SLOTS), f64), z((3, 3, KITTI_SLOTS), f64), z((3, 3, 3), f64), z((3, 3), f64)
+    p = lambda t: t.data_ptr() if t.numel() else None
+    scene = lambda: (p(doff_d), p(goff_d), p(poff_d), F, p(dt), p(dcl), nd, p(gtab), p(gty), ng, p(ov), npairs)
+    L = _native.lib()
+    with torch.cuda.device(dev):
+        s = _native.current_stream(dev)
+        _native.check(L.fcn_kitti_overlaps(*scene(), p(flags), s), "fcn_kitti_overlaps")
+        _native.check(L.fcn_kitti_pass_a(*scene(), mask, p(assigned), p(tp_score), p(tp_count), p(n_gt), s), "fcn_kitti_pass_a")
+        _native.check(L.fcn_kitti_thresholds(p(tp_score), p(tp_count), p(n_gt), ng, p(srt), p(thr), p(nthr), s), "fcn_kitti_thresholds")
+        _native.check(L.fcn_kitti_pass_b(*scene(), mask, p(thr), p(nthr), p(assigned), p(counts), p(sim), s), "fcn_kitti_pass_b")
+        _native.check(L.fcn_kitti_curves(p(counts), p(nthr), p(sim), F, p(flags), mask, p(prec), p(aos), p(ap), p(aos_ap), s),
+                      "fcn_kitti_curves")
+    for t in (doff_d, goff_d, poff_d, dt, dcl, gtab, gty, assigned, tp_score, srt, tp_count, sim):
+        t.record_stream(torch.cuda.current_stream(dev))
+    return {"precision": prec, "aos": aos, "ap": ap, "aos_ap": aos_ap, "thresholds": thr, "num_thresholds": nthr, "n_gt": n_gt,
+            "tp": counts[0], "fp": counts[1], "fn": counts[2], "overlaps": ov, "pair_off": poff, "flags": flags}
+
+
+def kitti_results(result, boxes2d, box_frame, types, num_frames=None):
+    """From what a detector returned to the CSR detection table of kitti_eval.  result: the dict of TwoStageDetector.detect_frames
+    (the second stage's dets / keep / cnt, stage1_row, stage1, kept), a dict with dets / keep / cnt / kept of a single-stage run
+    over the boxes `kept`, or the tuple (dets, valid, keep, cnt) of PointNetDet.detect over ALL boxes in order; boxes2d (D,4),
+    box_frame (D) and types (D): the 2-D detector's boxes, their frames and class names (host sequences; boxes2d may be a device
+    tensor); num_frames: F (default: the largest frame index + 1).  Only the keep lists are read back, as
+    SunrgbdDetector.detect_frames does.  The kept rows are ordered by frame (inside a frame: group after group in keep order).
+    Returns a dict: det_table (n,13), det_class (n) int32, ok (n) int32 (device); det_off (F+1), rows (n), row_box (n) int64
+    (host).  A row with ok == 0 (impossible behind the NMS, whose `valid` holds the same test) gets det_class -1 on the device
+    instead of being dropped."""
+    who = "kitti_results"
+    if isinstance(result, dict):
+        dets, keep, cnt = result["dets"], result["keep"], result["cnt"]
+        unit_box = np.asarray(result["kept"], dtype=np.int64).reshape(-1)
+        if "stage1_row" in result and dets is not None:
+            l1 = int(result["stage1"][0].shape[0]) // max(1, len(unit_box))          # rows per first-stage frustum
+            unit_box = unit_box[np.asarray(result["stage1_row"], dtype=np.int64) // l1]
+    else:
+        dets, _, keep, cnt = result
+        unit_box = np.arange(len(types), dtype=np.int64)
+    frame_all = torch.as_tensor(box_frame).cpu().numpy().reshape(-1).astype(np.int64)
+    if len(frame_all) != len(types) or (len(frame_all) and frame_all.min() < 0):
+        raise ValueError("%s: %d boxes have %d frames (all >= 0) and %d types" % (who, len(types), len(frame_all), len(types)))
+    F = int(num_frames) if num_frames is not None else (int(frame_all.max()) + 1 if len(frame_all) else 0)
+    if len(frame_all) and frame_all.max() >= F:
+        raise ValueError("%s: frame %d with num_frames = %d" % (who, frame_all.max(), F))
+    if dets is None:                                                             # nothing survived
+        dev = torch.as_tensor(boxes2d).device if torch.is_tensor(boxes2d) and boxes2d.is_cuda else torch.device("cuda")
+        zi = np.zeros((0,), dtype=np.int64)
+        return {"det_table": torch.zeros((0, 13), dtype=torch.float32, device=dev), "det_class": torch.zeros((0,), dtype=torch.int32, device=dev),
+                "ok": torch.zeros((0,), dtype=torch.int32, device=dev), "det_off": np.zeros((F + 1,), dtype=np.int64), "rows": zi, "row_box": zi}
+    _need_cuda(dets, who)
+    dev = dets.device
+    if len(unit_box) == 0 or dets.shape[0] % len(unit_box):
+        raise ValueError("%s: %d rows of dets do not divide into %d units" % (who, dets.shape[0], len(unit_box)))
+    l2 = int(dets.shape[0]) // len(unit_box)
+    keep_h, cnt_h = keep.cpu().numpy(), np.maximum(cnt.cpu().numpy().astype(np.int64), 0)
+    rows = np.concatenate([keep_h[g, :cnt_h[g]] for g in range(len(cnt_h))] + [np.zeros((0,), dtype=np.int64)]).astype(np.int64)
+    row_box = unit_box[rows // l2]
+    order = np.argsort(frame_all[row_box], kind="stable")
+    rows, row_box = rows[order], row_box[order]
+    det_off = np.concatenate([[0], np.cumsum(np.bincount(frame_all[row_box], minlength=F))]).astype(np.int64)
+    code = kitti_type_codes([types[i] for i in row_box], KITTI_CLASSES)
+    table, ok = kitti_label_rows(dets, rows, boxes2d, row_box)
+    cls = torch.from_numpy(np.where(code == len(KITTI_CLASSES), -1, code).astype(np.int32)).to(dev)
+    cls = torch.where(ok != 0, cls, torch.full_like(cls, -1))
+    return {"det_table": table, "det_class": cls, "ok": ok, "det_off": det_off, "rows": rows, "row_box": row_box}
 
 
 class SunrgbdDetector:

@@ -34,6 +34,9 @@
  *   fcn_decode_detections_rule  the same loop with the SUN-RGBD rule of train/test_net_det_sunrgbd.py:208-252
  *   fcn_box3d_corners           compute_box_3d, datasets/data_utils.py:44-70
  *   fcn_det_match, fcn_det_ap   eval_det_cls + voc_ap, train/sunrgbd_eval/eval_det.py:41-72,89-169
+ *   fcn_kitti_label_rows        write_detection_results + compute_alpha, train/test_net_det.py:88-105, provider_sample.py:389-394
+ *   fcn_kitti_overlaps, _pass_a, _thresholds, _pass_b, _curves
+ *                               the official KITTI evaluator, train/kitti_eval/evaluate_object_3d_offline.cpp
  *   fcn_stamp                   (measurement aid, no reference counterpart)
  *   fcn_stream_capture_id       (graph-capture bookkeeping of the Python layer, no reference counterpart)
  *
@@ -509,6 +512,66 @@ int fcn_det_match(const int32_t *det_off, const int32_t *gt_off, int G, const fl
  * for a class without a detection.  Integer cumulative counts; the curve, the envelope and the sum in fp64. */
 int fcn_det_ap(const int32_t *tp, const float *scores, const int32_t *det_class, int nd, const int32_t *npos, int C,
                int32_t *rank, double *rec, double *prec, double *ap, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * KITTI evaluation behind the NMS (csrc/kitti_eval.h).  The reference writes label-format text files
+ * (train/test_net_det.py:88-123) and shells out to train/kitti_eval/evaluate_object_3d_offline.cpp ("the evaluator" below), which
+ * clips every (detection, label) pair with boost polygons once per class x difficulty x metric x (1 + thresholds).  Here every
+ * pair is clipped once, in fp32, and nothing crosses to the host before the table.  Not restated: the %.4f / %f text round trip
+ * of the result files, the plots, the mail.
+ *   A LIST is k = (metric * 3 + class) * 3 + difficulty, 27 of them: metric 0 image, 1 ground, 2 3-D; class 0 car, 1 pedestrian,
+ *   2 cyclist; difficulty 0 easy, 1 moderate, 2 hard.  A list has 41 threshold SLOTS.
+ *   det_table (nd,13) float32 = alpha, x1,y1,x2,y2, h,w,l, tx,ty,tz, ry, score; det_class (nd) int32 in {0,1,2} (anything else:
+ *   a type that is not evaluated); gt_table (ng,14) float32 = truncation, occlusion, alpha, x1,y1,x2,y2, h,w,l, tx,ty,tz, ry;
+ *   gt_type (ng) int32: 0 Car, 1 Pedestrian, 2 Cyclist, 3 Van, 4 Person_sitting, 5 DontCare, 6 anything else.
+ *   The detections / labels of frame f are rows [det_off[f], det_off[f+1]) / [gt_off[f], gt_off[f+1]); its pairs start at
+ *   pair_off[f] = sum over the frames before it of (detections x labels); all three (F+1) int32 ON THE DEVICE, checked by the
+ *   caller on the host; the kernels clamp what they read to nd / ng / npairs (a frame whose pairs would not fit is empty).
+ *   ov (npairs,3) float32: the overlaps of pair (d, g) of frame f for the three metrics, at
+ *   pair_off[f] + (d - det_off[f]) * labels_of_f + (g - gt_off[f]).
+ *   class_mask: bit c set = class c is evaluated.
+ * Every entry: caller-owned buffers and workspace, stream-ordered, no allocation, no synchronisation; FCN_E_BADARG writes nothing.
+ * ------------------------------------------------------------------------------------------- */
+/* The label-format row of n kept rows of dets (num_dets,8) = tx, ty, tz, l, w, h, ry, score (train/test_net_det.py:88-105,284-293):
+ * rows (n) int32 picks them (NULL: rows 0 .. n-1), row_box (n) int32 the row of boxes2d (num_boxes,4) each came from.
+ * table (n,13) as det_table above, alpha = compute_alpha (datasets/provider_sample.py:389-394; evaluated in fp64, sign(0) = 0);
+ * ok (n) int32 = 0 where h, w or l < 0.01 (the reference drops such a row).  An index outside dets / boxes2d: NaN row, ok = 0. */
+int fcn_kitti_label_rows(const float *dets, int num_dets, const int32_t *rows, int n, const float *boxes2d, int num_boxes,
+                         const int32_t *row_box, float *table, int32_t *ok, void *stream);
+/* imageBoxOverlap (evaluator :229-263), groundBoxOverlap (:296-316) and box3DOverlap (:319-346; y extent t2 - h .. t2) of every
+ * pair of every frame, once: criterion -1 (union) against an ordinary label, criterion 0 (over the detection's own area / volume)
+ * against a DontCare label, the only one the protocol asks of such a pair (:582).
+ * flags (10) int32 (zeroed here): [metric * 3 + class] = 1 when the class has a detection with x1 >= 0 / tx != -1000 /
+ * ty != -1000 (:162-170: a class is only evaluated if it is detected), [9] = 1 when some alpha is -10 (:158: no AOS then). */
+int fcn_kitti_overlaps(const int32_t *det_off, const int32_t *gt_off, const int32_t *pair_off, int F, const float *det_table,
+                       const int32_t *det_class, int nd, const float *gt_table, const int32_t *gt_type, int ng, float *ov,
+                       int npairs, int32_t *flags, void *stream);
+/* cleanData (:383-456) + computeStatistics(compute_fp = false) (:458-555) for every (frame, list): the labels are walked in input
+ * order; each takes the unassigned candidate (class of the list, or below the minimum height: :449-454 look at the height first)
+ * with overlap > MIN_OVERLAP and the highest score, the first index among equal scores.
+ * assigned (27, nd, 2) int32 workspace (no initialisation needed); tp_score (27, ng) float32 + tp_count (27): the true positives'
+ * scores of each list in no particular order; n_gt (27) the labels counted.  tp_count and n_gt are zeroed here. */
+int fcn_kitti_pass_a(const int32_t *det_off, const int32_t *gt_off, const int32_t *pair_off, int F, const float *det_table,
+                     const int32_t *det_class, int nd, const float *gt_table, const int32_t *gt_type, int ng, float *ov, int npairs,
+                     int class_mask, int32_t *assigned, float *tp_score, int32_t *tp_count, int32_t *n_gt, void *stream);
+/* getThresholds (:348-381) of the 27 lists: sorted (27, ng) float32 workspace receives each list in descending order, the recall
+ * walk runs in fp64 as written.  thresholds (27,41) fp64 (0 behind the count), num_thresholds (27) int32. */
+int fcn_kitti_thresholds(const float *tp_score, const int32_t *tp_count, const int32_t *n_gt, int ng, float *sorted,
+                         double *thresholds, int32_t *num_thresholds, void *stream);
+/* cleanData + computeStatistics(compute_fp = true) (:458-616) for every (frame, list, slot < num_thresholds) in one launch.
+ * counts (3,27,41) int32 (zeroed here): tp, fp, fn; fp already without the detections a DontCare area holds (:558-591).
+ * sim (F,9,41) fp64: per frame, (class, difficulty) and slot the sum of (1 + cos(alpha_gt - alpha_det)) / 2 over the image metric's
+ * true positives in label order; slots < num_thresholds of evaluated classes are written, the rest is never read. */
+int fcn_kitti_pass_b(const int32_t *det_off, const int32_t *gt_off, const int32_t *pair_off, int F, const float *det_table,
+                     const int32_t *det_class, int nd, const float *gt_table, const int32_t *gt_type, int ng, float *ov, int npairs,
+                     int class_mask, const double *thresholds, const int32_t *num_thresholds, int32_t *assigned, int32_t *counts,
+                     double *sim, void *stream);
+/* The curves and the AP (:680-699, :716-720): precision (27,41) = tp / (tp + fp), aos (9,41) = sum over the frames, in frame order,
+ * of sim / (tp + fp); both filtered by the suffix maximum of std::max_element over all 41 entries (0 / 0 = NaN is kept as IEEE
+ * has it); ap (27) and aos_ap (9) = (entries 0, 4, .., 40 summed) / 11 * 100 in fp64 -- the reference sums in float for printing
+ * only, 11 * 2^-24 * 100 < 7e-5 away.  NaN rows for a class that flags / class_mask leave out; aos NaN when flags[9]. */
+int fcn_kitti_curves(const int32_t *counts, const int32_t *num_thresholds, const double *sim, int F, const int32_t *flags,
+                     int class_mask, double *precision, double *aos, double *ap, double *aos_ap, void *stream);
 
 /* Measurement aid: stores the device's constant-rate wall clock (100 MHz ticks) into *slot, in stream order. */
 int fcn_stamp(uint64_t *slot, void *stream);
