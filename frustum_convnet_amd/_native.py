@@ -81,13 +81,18 @@ class InpRefineDesc(ctypes.Structure):
                 ("stride", ctypes.c_double * 4), ("random_flip", ctypes.c_int32), ("random_shift", ctypes.c_int32)]
 
 
+class DrawDesc(ctypes.Structure):
+    _fields_ = [("B", ctypes.c_int32), ("N", ctypes.c_int32), ("random_flip", ctypes.c_int32), ("random_shift", ctypes.c_int32)]
+
+
 EXPORTS = ("fcn_arch", "fcn_build_hash", "fcn_stat_replicas", "fcn_query_depth_point_f32", "fcn_query_depth_point_multi_f32", "fcn_pn_wgrad_rows", "fcn_pn_compact", "fcn_pn_group_compact", "fcn_pn_group_compact2",
            "fcn_pn_pack_weights", "fcn_pn_pack_weights_all", "fcn_pn_infer_fold", "fcn_pn_infer", "fcn_pn_forward", "fcn_pn_backward", "fcn_pn_backward2", "fcn_pn_backward3", "fcn_pn_backward_dense", "fcn_pn_conv_fwd", "fcn_det_loss_tail", "fcn_det_loss_tail_rows", "fcn_det_loss_tail_rows2", "fcn_det_iou_metrics",
            "fcn_det_loss_tail_scratch_floats", "fcn_adam_step_f32", "fcn_sgd_step_f32", "fcn_adam_step_slots", "fcn_prepare_inputs", "fcn_prepare_inputs_refine", "fcn_prepare_inputs_sunrgbd", "fcn_refine_select_count", "fcn_refine_select_fill", "fcn_prepare_inputs_infer", "fcn_frustum_select_seg", "fcn_frustum_select_count", "fcn_frustum_select_fill", "fcn_frustum_label_count", "fcn_frustum_label_fill", "fcn_frustum_sunrgbd_count", "fcn_frustum_sunrgbd_fill", "fcn_frustum_sunrgbd_label_count", "fcn_frustum_sunrgbd_label_fill", "fcn_frustum_subset_pos", "fcn_prepare_inputs_sunrgbd_infer", "fcn_refine_match", "fcn_refine_label_count", "fcn_refine_label_fill", "fcn_stamp", "fcn_stream_capture_id",
            "fcn_convnet_sizes", "fcn_convnet_logits_ld", "fcn_convnet_pack", "fcn_convnet_forward", "fcn_convnet_forward2",
            "fcn_convnet_backward", "fcn_box3d_iou_pair_f32", "fcn_decode_detections", "fcn_rotate_nms_3d",
            "fcn_decode_detections_rule", "fcn_box3d_corners", "fcn_det_match", "fcn_det_ap",
-           "fcn_kitti_label_rows", "fcn_kitti_overlaps", "fcn_kitti_pass_a", "fcn_kitti_thresholds", "fcn_kitti_pass_b", "fcn_kitti_curves")
+           "fcn_kitti_label_rows", "fcn_kitti_overlaps", "fcn_kitti_pass_a", "fcn_kitti_thresholds", "fcn_kitti_pass_b", "fcn_kitti_curves",
+           "fcn_draw_batch", "fcn_draw_limits")
 
 _lib = None
 
@@ -275,6 +280,11 @@ def lib():
         L.fcn_kitti_pass_b.argtypes = ks_in + [ctypes.c_int] + [c_fp] * 6
         L.fcn_kitti_curves.restype = ctypes.c_int
         L.fcn_kitti_curves.argtypes = [c_fp] * 3 + [ctypes.c_int, c_fp, ctypes.c_int] + [c_fp] * 5
+    if hasattr(L, "fcn_draw_batch") or "FCN_LIB_NAME" not in os.environ:       # (A/B builds of older kernel sources lack them)
+        L.fcn_draw_batch.restype = ctypes.c_int
+        L.fcn_draw_batch.argtypes = [ctypes.POINTER(DrawDesc)] + [c_fp] * 3 + [ctypes.c_uint64] + [c_fp] * 7
+        L.fcn_draw_limits.restype = ctypes.c_int
+        L.fcn_draw_limits.argtypes = [ctypes.POINTER(ctypes.c_int)] * 2
     L.fcn_rotate_nms_3d.restype = ctypes.c_int
     L.fcn_rotate_nms_3d.argtypes = [c_fp] * 3 + [ctypes.c_int] * 3 + [ctypes.c_float, ctypes.c_int] + [c_fp] * 3
     _lib = L

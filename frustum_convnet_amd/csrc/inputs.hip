@@ -468,3 +468,8 @@ extern "C" int fcn_prepare_inputs_refine(const fcn_inp_refine_desc *d, const flo
 // First-stage detections + the frames' label boxes -> the refinement stage's TRAINING records: match, enlarge, jitter, select, count
 // the positives (fcn_refine_match, fcn_refine_label_count / _fill): csrc/refine_label.h
 #include "refine_label.h"
+
+// ------------------------------------------------------------------------------------------------
+// The random draws the prepare kernels above read -- resample indices, flip coin, depth-shift normal, height shift -- made on the
+// device by a counter-based generator (fcn_draw_batch, fcn_draw_limits): csrc/draws.h
+#include "draws.h"

@@ -5,9 +5,10 @@ Host-side mirror of the reference's loader for this step (datasets/provider_samp
 (:396-397) stacks them; here the raw records of a batch go to the GPU in ONE packed upload and one kernel launch writes
 the dict PointNetDet.forward consumes (same keys, shapes and dtypes as the reference's collated batch).
 
-Randomness stays on the host and follows the reference's call order per sample -- np.random.choice (resample),
+By default randomness stays on the host and follows the reference's call order per sample -- np.random.choice (resample),
 np.random.random (flip coin), np.random.randn (depth shift) -- so with the same numpy seed the batch equals the
-reference's batch (tests/test_gpu_inputs.py checks that against the golden fixture).
+reference's batch (tests/test_gpu_inputs.py checks that against the golden fixture).  DeviceDraws makes the same draws on the
+device from a counter-based stream of its own (C-ABI fcn_draw_batch, csrc/draws.h): every builder takes one as `draws=`.
 """
 import ctypes
 
@@ -32,6 +33,105 @@ def draw(counts, npoints, random_flip=True, random_shift=True, rng=np.random):
     return np.stack(choice).astype(np.int32), np.asarray(coin, dtype=np.float64), np.asarray(normal, dtype=np.float64)
 
 
+class DeviceDraws:
+    """The same draws made ON THE DEVICE by a counter-based generator (C-ABI fcn_draw_batch, csrc/draws.h): one launch writes
+    choice (B,N) int32, coin, normal (and hshift) (B) float64 where fcn_prepare_inputs* reads them -- no host read of the counts, no
+    upload, capturable.  The stream is Philox4x32-10 keyed by `seed` and counted by the device-resident step counter `state`
+    (INTEGRATION.md "Random draws on the device" states the contract bit for bit); it is NOT numpy's, so the host draw() stays the
+    default of every builder and the path the golden fixtures check.  Pass an instance as `draws=` to a builder.
+    state: (1,) int64 -- every draw() reads it and leaves it one higher, in stream order; writing a value back reproduces that
+    draw.  status: (1,) int32 -- bit 0 is set by a row nothing could be drawn from (see check())."""
+
+    def __init__(self, seed, device="cuda"):
+        self.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError("frustum_convnet_amd: the device draws are a HIP kernel (MI355X only); no CPU fallback")
+        self.state = torch.zeros((1,), dtype=torch.int64, device=self.device)
+        self.status = torch.zeros((1,), dtype=torch.int32, device=self.device)
+
+    @staticmethod
+    def limits():
+        """(the largest npoints, the row count up to which a row is sorted whole in LDS) of fcn_draw_batch."""
+        a, b = ctypes.c_int(0), ctypes.c_int(0)
+        _native.check(_native.lib().fcn_draw_limits(ctypes.byref(a), ctypes.byref(b)), "fcn_draw_limits")
+        return a.value, b.value
+
+    @staticmethod
+    def _want(name, t, dtype, numel=None):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise ValueError("DeviceDraws.draw: %s must be a device tensor" % name)
+        if t.dtype != dtype or not t.is_contiguous():
+            raise ValueError("DeviceDraws.draw: %s must be a contiguous %s tensor, got %s" % (name, dtype, t.dtype))
+        if numel is not None and t.numel() != numel:
+            raise ValueError("DeviceDraws.draw: %s must hold %d elements, got %s" % (name, numel, tuple(t.shape)))
+        return t
+
+    def draw(self, counts, npoints, random_flip, random_shift, hshift=False, sub=None, sub_off=None, out=None):
+        """counts (B,) int64 on the device: the rows of each sample.  -> (choice (B,npoints) int32, coin (B), normal (B) float64
+        [, hshift (B) float64 when hshift]) on the device, into `out` (a tuple of that shape) when given: then there is no
+        allocation and no host read, only the two launches -- capturable.  sub (packed int32) / sub_off (B+1 int64), both or
+        neither: a sample with a non-empty slice draws from the slice's length and gets sub's values (SUN-RGBD's frustum subsample).
+        A sample without a row gets zeros and flags `status`: see check()."""
+        N = int(npoints)
+        self._want("counts", counts, torch.int64)
+        B = int(counts.numel())
+        if B <= 0 or N <= 0:
+            raise ValueError("DeviceDraws.draw: %d samples of %d points" % (B, N))
+        if (sub is None) != (sub_off is None):
+            raise ValueError("DeviceDraws.draw: sub and sub_off go together")
+        if sub is not None:
+            self._want("sub", sub, torch.int32)
+            self._want("sub_off", sub_off, torch.int64, B + 1)
+        if out is None:
+            f64 = dict(dtype=torch.float64, device=self.device)
+            out = (torch.empty((B, N), dtype=torch.int32, device=self.device), torch.empty((B,), **f64), torch.empty((B,), **f64))
+            if hshift:
+                out = out + (torch.empty((B,), **f64),)
+        if len(out) != (4 if hshift else 3):
+            raise ValueError("DeviceDraws.draw: out must hold %d tensors" % (4 if hshift else 3))
+        self._want("out[0] (choice)", out[0], torch.int32, B * N)
+        for name, t in zip(("coin", "normal", "hshift"), out[1:]):
+            self._want("out (%s)" % name, t, torch.float64, B)
+        desc = _native.DrawDesc(B, N, 1 if random_flip else 0, 1 if random_shift else 0)
+        p = lambda x: None if x is None else x.data_ptr()
+        with torch.cuda.device(self.device):
+            _native.check(_native.lib().fcn_draw_batch(
+                ctypes.byref(desc), p(counts), p(sub), p(sub_off), self.seed, p(self.state), p(out[0]), p(out[1]), p(out[2]),
+                p(out[3]) if hshift else None, p(self.status), _native.current_stream(self.device)), "fcn_draw_batch")
+        stream = torch.cuda.current_stream(self.device)
+        for t in (counts, sub, sub_off):
+            if t is not None:
+                t.record_stream(stream)
+        return tuple(out)
+
+    def check(self):
+        """Reads `status` (a synchronisation: not for a captured region) and raises ValueError when a draw since the last check()
+        met a sample with no row, or with 2^31 rows or more; the word is cleared."""
+        s = int(self.status.cpu()[0])
+        if s:
+            self.status.zero_()
+            raise ValueError("DeviceDraws: a sample had no row to draw from (or 2^31 rows or more): its choice row is zeros")
+
+
+def _is_device_draws(draws):
+    """A tuple of device tensors: used as it is (no np.asarray, no upload)."""
+    return isinstance(draws, (tuple, list)) and len(draws) > 0 and all(isinstance(x, torch.Tensor) and x.is_cuda for x in draws)
+
+
+def _draw_tensors(draws, dev, n):
+    """draws as the n device tensors the prepare kernels read: device tensors as they are, host arrays uploaded."""
+    if _is_device_draws(draws):
+        return tuple(draws[:n])
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev, non_blocking=True)
+    return (up(np.asarray(draws[0], dtype=np.int32)),) + tuple(up(np.asarray(x, dtype=np.float64)) for x in draws[1:n])
+
+
+def _row_counts(off):
+    """(B+1,) offsets on the device -> (B,) int64 row counts on the device."""
+    return (off[1:] - off[:-1]).to(torch.int64).contiguous()
+
+
 class InputBuilder:
     """npoints / strides / max_depth as cfg.DATA.{NUM_SAMPLES, STRIDE, MAX_DEPTH}; one_hot over the dataset's classes."""
 
@@ -49,7 +149,8 @@ class InputBuilder:
     def build(self, records, draws=None, with_seg=True):
         """records: list of dicts with RECORD_KEYS (points (n,>=3) float32 in rect camera coordinates, seg (n,), box2d (4,),
         P (3,4), box3d (8,3) corners, heading, size (l,w,h), frustum_angle, type).  draws: (choice (B,N) int32, coin (B),
-        normal (B)) or None to draw like the reference.  Returns the batch dict on the device.
+        normal (B)) -- host arrays, or device tensors used as they are -- a DeviceDraws to draw on the device, or None to draw like
+        the reference (here and wherever a builder takes `draws`).  Returns the batch dict on the device.
         = upload() (host -> device copies of the raw records and the draws) + launch() (the kernel)."""
         return self.launch(self.upload(records, draws, with_seg))
 
@@ -62,17 +163,18 @@ class InputBuilder:
         counts = [len(r["points"]) for r in records]
         if draws is None:
             draws = draw(counts, N, self.random_flip, self.random_shift)
-        choice, coin, normal = draws
         stride = int(records[0]["points"].shape[1])
         raw = np.concatenate([np.ascontiguousarray(r["points"], dtype=np.float32) for r in records], 0)
         off = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
         f64 = lambda k, shape: np.stack([np.asarray(r[k], dtype=np.float64).reshape(shape) for r in records])
         dev = self.device
         up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev, non_blocking=True)
-        t = {"raw": up(raw), "off": up(off), "choice": up(np.asarray(choice, dtype=np.int32)),
+        t = {"raw": up(raw), "off": up(off),
              "fangle": up(f64("frustum_angle", ())), "box2d": up(f64("box2d", (4,))), "P": up(f64("P", (12,))),
-             "corners": up(f64("box3d", (24,))), "heading": up(f64("heading", ())), "size": up(f64("size", (3,))),
-             "coin": up(np.asarray(coin, dtype=np.float64)), "normal": up(np.asarray(normal, dtype=np.float64))}
+             "corners": up(f64("box3d", (24,))), "heading": up(f64("heading", ())), "size": up(f64("size", (3,)))}
+        if isinstance(draws, DeviceDraws):          # drawn on the device from the uploaded offsets (re-draw into these any time)
+            draws = draws.draw(_row_counts(t["off"]), N, self.random_flip, self.random_shift)
+        t["choice"], t["coin"], t["normal"] = _draw_tensors(draws, dev, 3)
         t["seg"] = up(np.concatenate([np.asarray(r["seg"]).astype(np.int64) for r in records], 0)) if with_seg else None
         size_class = [self.classes.index(r["type"]) for r in records]
         t["size_class"] = torch.tensor(size_class, dtype=torch.int64).view(B, 1).to(dev, non_blocking=True)
@@ -152,8 +254,10 @@ class InputBuilder:
         up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev, non_blocking=True)
         idx = up(kept)
         pick = lambda x: x.index_select(0, idx).contiguous()
+        if isinstance(draws, DeviceDraws):
+            draws = draws.draw(pick(_row_counts(sel["off"])), N, False, False)
         Pd = torch.as_tensor(P).to(device=dev, dtype=torch.float64).reshape(-1, 12)
-        t = {"raw": sel["points"], "choice": up(np.asarray(draws[0], dtype=np.int32)),
+        t = {"raw": sel["points"], "choice": _draw_tensors(draws, dev, 1)[0],
              "off": pick(sel["off"]),                                         # the kernel reads a sample's first row only
              "fangle": pick(sel["frustum_angle"]), "box2d": pick(sel["box2d"]),
              "P": Pd.index_select(0, pick(sel["box_frame"]).to(torch.int64)).contiguous()}
@@ -194,15 +298,16 @@ class InputBuilder:
             return {"kept": kept}
         if draws is None:
             draws = draw(sel["counts"], self.npoints, self.random_flip, self.random_shift)
-        choice, coin, normal = draws
         dev = self.device
+        if isinstance(draws, DeviceDraws):
+            draws = draws.draw(_row_counts(sel["off"]), self.npoints, self.random_flip, self.random_shift)
+        choice, coin, normal = _draw_tensors(draws, dev, 3)
         up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev, non_blocking=True)
         Pd = torch.as_tensor(P).to(device=dev, dtype=torch.float64).reshape(-1, 12)
         t = {"raw": sel["points"], "off": sel["off"], "seg": sel["seg"] if with_seg else None,
-             "choice": up(np.asarray(choice, dtype=np.int32)), "fangle": sel["frustum_angle"], "box2d": sel["box2d"],
+             "choice": choice, "fangle": sel["frustum_angle"], "box2d": sel["box2d"],
              "P": Pd.index_select(0, sel["box_frame"].to(torch.int64)).contiguous(), "corners": sel["box3d"].reshape(K, 24),
-             "heading": sel["heading"], "size": sel["size"], "coin": up(np.asarray(coin, dtype=np.float64)),
-             "normal": up(np.asarray(normal, dtype=np.float64))}
+             "heading": sel["heading"], "size": sel["size"], "coin": coin, "normal": normal}
         size_class = [self.classes.index(types[i]) for i in kept]
         t["size_class"] = torch.tensor(size_class, dtype=torch.int64).view(K, 1).to(dev, non_blocking=True)
         if self.one_hot:
@@ -259,18 +364,19 @@ class SunrgbdInputBuilder:
         counts = [len(r["points"]) for r in records]
         if draws is None:
             draws = draw_sunrgbd(counts, N, self.random_flip, self.random_shift)
-        choice, coin, normal, hshift = draws
         stride = int(records[0]["points"].shape[1])
         raw = np.concatenate([np.ascontiguousarray(r["points"], dtype=np.float32) for r in records], 0)
         off = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
         f64 = lambda k, shape: np.stack([np.asarray(r[k], dtype=np.float64).reshape(shape) for r in records])
         dev = self.device
         up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev, non_blocking=True)
-        t = {"raw": up(raw), "off": up(off), "choice": up(np.asarray(choice, dtype=np.int32)),
+        t = {"raw": up(raw), "off": up(off),
              "fangle": up(f64("frustum_angle", ())), "box2d": up(f64("box2d", (4,))), "K": up(f64("K", (9,))),
              "R": up(f64("Rtilt", (9,))), "corners": up(f64("box3d", (24,))), "heading": up(f64("heading", ())),
-             "size": up(f64("size", (3,))), "coin": up(np.asarray(coin, dtype=np.float64)),
-             "normal": up(np.asarray(normal, dtype=np.float64)), "hshift": up(np.asarray(hshift, dtype=np.float64))}
+             "size": up(f64("size", (3,)))}
+        if isinstance(draws, DeviceDraws):
+            draws = draws.draw(_row_counts(t["off"]), N, self.random_flip, self.random_shift, hshift=True)
+        t["choice"], t["coin"], t["normal"], t["hshift"] = _draw_tensors(draws, dev, 4)
         seg_raw = None
         if with_seg:
             seg_raw = up(np.concatenate([np.asarray(r["seg"]).astype(np.int64) for r in records], 0))
@@ -315,6 +421,26 @@ class SunrgbdInputBuilder:
                 choice[b] = np.asarray(ix, dtype=np.int32)[choice[b]]
         return choice
 
+    def _device_draw(self, dd, cnt, sub, flip, shift):
+        """dd.draw over the records' rows with the frustum subsamples composed in the kernel: cnt (B,) the boxes' full row counts
+        on the device, sub: per box the host's subsample indices or None -- packed and uploaded (a box without one draws from
+        its cnt rows)."""
+        dev = self.device
+        counts = cnt.to(torch.int64).contiguous()
+        if all(ix is None for ix in sub):
+            return dd.draw(counts, self.npoints, flip, shift, hshift=True)
+        lens = [0 if ix is None else len(ix) for ix in sub]
+        sub_off = torch.from_numpy(np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)).to(dev, non_blocking=True)
+        flat = torch.from_numpy(np.concatenate([np.asarray(ix, dtype=np.int32) for ix in sub if ix is not None])).to(dev, non_blocking=True)
+        return dd.draw(counts, self.npoints, flip, shift, hshift=True, sub=flat, sub_off=sub_off)
+
+    def _choice(self, draws, sub):
+        """The choice table the kernel reads: a device tensor as it is -- indices into the full packed selection, as
+        DeviceDraws writes them through `sub` -- a host table composed with the subsamples and uploaded."""
+        if _is_device_draws(draws):
+            return draws[0]
+        return torch.from_numpy(np.ascontiguousarray(self._compose(draws[0], sub))).to(self.device, non_blocking=True)
+
     def _calib_rows(self, K, Rtilt, box_frame):
         dev = self.device
         idx = box_frame.to(torch.int64)
@@ -348,8 +474,10 @@ class SunrgbdInputBuilder:
         up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev, non_blocking=True)
         idx = up(kept)
         pick = lambda x: x.index_select(0, idx).contiguous()
+        if isinstance(draws, DeviceDraws):
+            draws = self._device_draw(draws, pick(sel["cnt"]), [sel["sub"][d] for d in kept], False, False)
         Kd, Rd = self._calib_rows(K, Rtilt, pick(sel["box_frame"]))
-        t = {"raw": sel["points"], "choice": up(self._compose(draws[0], [sel["sub"][d] for d in kept])),
+        t = {"raw": sel["points"], "choice": self._choice(draws, [sel["sub"][d] for d in kept]),
              "off": pick(sel["off"]),                                         # the kernel reads a sample's first row only
              "fangle": pick(sel["frustum_angle"]), "box2d": pick(sel["box2d"]), "K": Kd, "R": Rd}
         f32 = dict(dtype=torch.float32, device=dev)
@@ -391,14 +519,15 @@ class SunrgbdInputBuilder:
             return {"kept": kept}
         if draws is None:
             draws = draw_sunrgbd(subsampled_counts(sel["counts"], sel["sub"]), N, self.random_flip, self.random_shift)
-        choice, coin, normal, hshift = draws
         dev = self.device
+        if isinstance(draws, DeviceDraws):
+            draws = self._device_draw(draws, sel["cnt"], sel["sub"], self.random_flip, self.random_shift)
+        coin, normal, hshift = _draw_tensors(draws, dev, 4)[1:]
         up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev, non_blocking=True)
         Kd, Rd = self._calib_rows(K, Rtilt, sel["box_frame"])
-        t = {"raw": sel["points"], "off": sel["off"], "choice": up(self._compose(choice, sel["sub"])), "fangle": sel["frustum_angle"],
+        t = {"raw": sel["points"], "off": sel["off"], "choice": self._choice(draws, sel["sub"]), "fangle": sel["frustum_angle"],
              "box2d": sel["box2d"], "K": Kd, "R": Rd, "corners": sel["box3d"].reshape(B, 24), "heading": sel["heading"],
-             "size": sel["size"], "coin": up(np.asarray(coin, dtype=np.float64)), "normal": up(np.asarray(normal, dtype=np.float64)),
-             "hshift": up(np.asarray(hshift, dtype=np.float64))}
+             "size": sel["size"], "coin": coin, "normal": normal, "hshift": hshift}
         seg_raw = sel["seg"] if with_seg else None
         f32 = dict(dtype=torch.float32, device=dev)
         out = {"point_cloud": torch.empty((B, 3, N), **f32), "rot_angle": torch.empty((B, 1), **f32),
@@ -558,7 +687,9 @@ class RefineInputBuilder:
         sel = None if B == D else up(kept)
         pick = lambda x: x.contiguous() if sel is None else x.index_select(0, sel).contiguous()
         off = cands["off"]
-        t = {"raw": cands["points"], "choice": up(np.asarray(draws[0], dtype=np.int32)),
+        if isinstance(draws, DeviceDraws):
+            draws = draws.draw(pick(_row_counts(off)), N, False, False)
+        t = {"raw": cands["points"], "choice": _draw_tensors(draws, dev, 1)[0],
              # the kernel reads a sample's first row only: the survivors' starts (+ the end of the last one, for the (B+1) form)
              "off": off if sel is None else torch.cat([off.index_select(0, sel), off[int(kept[-1]) + 1:int(kept[-1]) + 2]]),
              "pcorners": pick(cands["pred_box3d"]), "pangle": pick(cands["pred_angle"]), "psize": pick(cands["pred_size"])}
@@ -587,14 +718,15 @@ class RefineInputBuilder:
             return {"kept": kept}
         if draws is None:
             draws = draw_refine(sel["counts"], self.npoints, self.random_flip, self.random_shift)
-        choice, coin, normal = draws
         dev = self.device
-        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev, non_blocking=True)
+        if isinstance(draws, DeviceDraws):
+            draws = draws.draw(_row_counts(sel["off"]), self.npoints, self.random_flip, self.random_shift)
+        choice, coin, normal = _draw_tensors(draws, dev, 3)
         widths = sel["pred_size"][:, 1].cpu().numpy()                         # K numbers: the tensor shapes depend on them
-        t = {"raw": sel["points"], "off": sel["off"], "choice": up(np.asarray(choice, dtype=np.int32)),
+        t = {"raw": sel["points"], "off": sel["off"], "choice": choice,
              "pcorners": sel["pred_box3d"].reshape(K, 24), "pangle": sel["pred_angle"], "psize": sel["pred_size"],
              "corners": sel["box3d"].reshape(K, 24), "heading": sel["heading"], "size": sel["size"],
-             "coin": up(np.asarray(coin, dtype=np.float64)), "normal": up(np.asarray(normal, dtype=np.float64))}
+             "coin": coin, "normal": normal}
         out = self._launch(t, K, int(sel["points"].shape[1]), self._lpad(widths), True)
         size_class = [self.classes.index(types[i]) for i in sel["unit_cand"]]
         out["size_class"] = torch.tensor(size_class, dtype=torch.int64).view(K, 1).to(dev, non_blocking=True)
@@ -612,7 +744,6 @@ class RefineInputBuilder:
         counts = [len(r["points"]) for r in records]
         if draws is None:
             draws = draw_refine(counts, N, self.random_flip and with_labels, self.random_shift and with_labels)
-        choice, coin, normal = draws
         stride = int(records[0]["points"].shape[1])
         raw = np.concatenate([np.ascontiguousarray(r["points"], dtype=np.float32) for r in records], 0)
         off = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
@@ -622,11 +753,15 @@ class RefineInputBuilder:
         Lpad = self._lpad(psize[:, 1])
         dev = self.device
         up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev, non_blocking=True)
-        t = {"raw": up(raw), "off": up(off), "choice": up(np.asarray(choice, dtype=np.int32)),
+        t = {"raw": up(raw), "off": up(off),
              "pcorners": up(f64("pred_box3d", (24,))), "pangle": up(f64("pred_angle", ())), "psize": up(psize)}
+        if isinstance(draws, DeviceDraws):
+            draws = draws.draw(_row_counts(t["off"]), N, self.random_flip and with_labels, self.random_shift and with_labels)
+        choice, coin, normal = _draw_tensors(draws, dev, 3)
+        t["choice"] = choice
         if with_labels:
             t.update(corners=up(f64("box3d", (24,))), heading=up(f64("heading", ())), size=up(f64("size", (3,))),
-                     coin=up(np.asarray(coin, dtype=np.float64)), normal=up(np.asarray(normal, dtype=np.float64)))
+                     coin=coin, normal=normal)
         out = self._launch(t, B, stride, Lpad, with_labels)
         size_class = [self.classes.index(r["type"]) for r in records]
         if with_labels:

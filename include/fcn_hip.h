@@ -667,6 +667,32 @@ int fcn_prepare_inputs_refine(const fcn_inp_refine_desc *d, const float *raw_pts
                               float *box3d_size, float *rot_angle, float *ref_center, int32_t *lens, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * The random draws fcn_prepare_inputs* reads -- choice (B,N) int32, coin (B), normal (B) and, for SUN-RGBD, hshift (B) fp64 -- made
+ * on the device (csrc/draws.h) instead of by np.random on the host (datasets/provider_sample.py:165-168, :225, :238;
+ * provider_sample_sunrgbd.py:144, :211, :224, :228).  The stream is a counter-based one, not numpy's; the contract, bit for bit
+ * (INTEGRATION.md "Random draws on the device"; tests/draws_ref.py restates it in numpy):
+ *   Philox4x32-10, key (seed lo, seed hi), counter (i, b, step lo, ((step >> 32) << 2) | tag); b the row, step = state[0] (< 2^62).
+ *   n >= N (tag 0): key k_j = word j & 3 of block j >> 2; choice[b, :] = the j of the N smallest (k_j << 32) | j, ascending.
+ *   0 < n < N (tag 1): choice[b, i] = (w * n) >> 32, w = word i & 3 of block i >> 2.
+ *   tag 2, blocks 0 and 1 (w0..w7), u(x, y) = ((x >> 5) * 2^26 + (y >> 6)): coin = u(w0, w1) * 2^-53; u1 = (u(w2, w3) + 1) * 2^-53,
+ *   u2 = u(w4, w5) * 2^-53, normal = sqrt(-2 ln u1) * cos(2 pi u2); hshift = u(w6, w7) * 2^-53.  random_flip == 0: coin = 0.0;
+ *   random_shift == 0: normal = 0.0 and hshift = 0.5 (what inputs.draw*() give).
+ * counts (B) int64: the rows n of each sample.  sub (packed int32) + sub_off (B+1) int64, both or neither: where
+ * sub_off[b + 1] > sub_off[b], row b's n is that length and the value written is sub[sub_off[b] + c] instead of c.
+ * A row with n <= 0 or n >= 2^31 gets choice = 0 throughout and sets bit 0 of *status (int32, device; never cleared here).
+ * state (1) int64, device: read by every row, state[0] + 1 left behind in stream order (a second one-thread launch), so a replayed
+ * capture draws anew and writing state[0] back reproduces a draw.  hshift may be NULL.  Capturable: no allocation, no host read.
+ * B <= 0, N <= 0, a NULL required pointer or only one of sub / sub_off: FCN_E_BADARG; N > 2048: FCN_E_LIMIT; nothing is written. */
+typedef struct fcn_draw_desc {
+    int32_t B, N;                /* samples, indices per sample */
+    int32_t random_flip, random_shift;
+} fcn_draw_desc;
+int fcn_draw_batch(const fcn_draw_desc *d, const int64_t *counts, const int32_t *sub, const int64_t *sub_off, uint64_t seed,
+                   int64_t *state, int32_t *choice, double *coin, double *normal, double *hshift, int32_t *status, void *stream);
+/* The largest N of fcn_draw_batch and the row count up to which a row is sorted whole in LDS (above it: radix select first). */
+int fcn_draw_limits(int *max_n, int *sort_cap);
+
+/* ---------------------------------------------------------------------------------------------
  * The link between the two stages of the cascade: first-stage detections -> the raw points of the refinement stage.  Replaces
  * the host loop of kitti/prepare_data_refine.py::extract_frustum_data_rgb_detection (:649-773): enlarge every predicted box by
  * `ratio` (1.2 there), keep the frame's points inside it (scipy.spatial.Delaunay(...).find_simplex), pickle them for
