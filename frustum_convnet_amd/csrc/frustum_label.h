@@ -140,11 +140,15 @@ template <bool V4> __global__ __launch_bounds__(FS_T) void fl_fill_kernel(FlArgs
     }
 }
 
-extern "C" int fcn_frustum_label_count(const float *frame_pts, const int64_t *frame_off, int F, int pt_stride, const double *P,
-                                       const double *V2C, const double *R0, const double *img_wh, const double *boxes,
-                                       const int32_t *box_frame, int D, int S, int clip_boxes, double clip_distance,
-                                       const double *gt_box3d, double *box2d, double *frustum_angle, int32_t *seg_cnt,
-                                       int32_t *seg_pos, double *corners, void *stream)
+// What the entries below and the no-read pair of frustum_plan.h (fcn_frustum_train_count / _fill) share: the argument checks, the
+// kernels' arguments and the launch.  read_lists: read box_frame and frame_off back first (fs_read_lists: a synchronisation) and
+// report an out-of-range frame or a frame longer than S segments; without it nothing is read and 0 is returned once the launch is
+// enqueued -- the kernels skip a box whose frame is out of range either way, the length condition is the caller's then.
+static inline int fl_count_launch(const float *frame_pts, const int64_t *frame_off, int F, int pt_stride, const double *P,
+                                  const double *V2C, const double *R0, const double *img_wh, const double *boxes,
+                                  const int32_t *box_frame, int D, int S, int clip_boxes, double clip_distance,
+                                  const double *gt_box3d, double *box2d, double *frustum_angle, int32_t *seg_cnt,
+                                  int32_t *seg_pos, double *corners, void *stream, bool read_lists)
 {
     if (pt_stride < 3 || D < 0 || F < 0 || S < 1 || D > FS_MAX_D) return FCN_E_BADARG;
     if (D == 0) return 0;
@@ -157,8 +161,11 @@ extern "C" int fcn_frustum_label_count(const float *frame_pts, const int64_t *fr
     if (!frame_pts || !frame_off || !P || !V2C || !R0 || !img_wh || !boxes || !box_frame || !gt_box3d || !box2d || !frustum_angle ||
         !corners)
         return FCN_E_BADARG;
-    bool ok = false, fits = false;
-    FCN_TRY(fs_read_lists(box_frame, frame_off, D, F, S, (hipStream_t)stream, &ok, &fits));
+    bool ok = true, fits = true;
+    if (read_lists) {
+        ok = false; fits = false;
+        FCN_TRY(fs_read_lists(box_frame, frame_off, D, F, S, (hipStream_t)stream, &ok, &fits));
+    }
     if (!fits) return FCN_E_BADARG;
     FlArgs a;
     a.s.pts = frame_pts; a.s.foff = frame_off; a.s.P = P; a.s.V2C = V2C; a.s.R0 = R0; a.s.wh = img_wh; a.s.boxes = boxes;
@@ -173,19 +180,22 @@ extern "C" int fcn_frustum_label_count(const float *frame_pts, const int64_t *fr
     return ok ? 0 : FCN_E_BADARG;
 }
 
-extern "C" int fcn_frustum_label_fill(const float *frame_pts, const int64_t *frame_off, int F, int pt_stride, const double *P,
-                                      const double *V2C, const double *R0, const double *img_wh, const double *boxes,
-                                      const int32_t *box_frame, int D, int S, int clip_boxes, double clip_distance,
-                                      const double *gt_box3d, const int64_t *seg_off, float *out_pts, int64_t *out_seg,
-                                      void *stream)
+static inline int fl_fill_launch(const float *frame_pts, const int64_t *frame_off, int F, int pt_stride, const double *P,
+                                 const double *V2C, const double *R0, const double *img_wh, const double *boxes,
+                                 const int32_t *box_frame, int D, int S, int clip_boxes, double clip_distance,
+                                 const double *gt_box3d, const int64_t *seg_off, float *out_pts, int64_t *out_seg, void *stream,
+                                 bool read_lists)
 {
     if (pt_stride < 3 || D < 0 || F < 0 || S < 1 || D > FS_MAX_D) return FCN_E_BADARG;
     if (D == 0 || F == 0) return 0;
     if (!frame_pts || !frame_off || !P || !V2C || !R0 || !img_wh || !boxes || !box_frame || !gt_box3d || !seg_off || !out_pts ||
         !out_seg)
         return FCN_E_BADARG;
-    bool ok = false, fits = false;
-    FCN_TRY(fs_read_lists(box_frame, frame_off, D, F, S, (hipStream_t)stream, &ok, &fits));
+    bool ok = true, fits = true;
+    if (read_lists) {
+        ok = false; fits = false;
+        FCN_TRY(fs_read_lists(box_frame, frame_off, D, F, S, (hipStream_t)stream, &ok, &fits));
+    }
     if (!fits) return FCN_E_BADARG;
     FlArgs a;
     a.s.pts = frame_pts; a.s.foff = frame_off; a.s.P = P; a.s.V2C = V2C; a.s.R0 = R0; a.s.wh = img_wh; a.s.boxes = boxes;
@@ -198,4 +208,24 @@ extern "C" int fcn_frustum_label_fill(const float *frame_pts, const int64_t *fra
         hipLaunchKernelGGL(fl_fill_kernel<false>, dim3(S, D), dim3(FS_T), 0, (hipStream_t)stream, a);
     FCN_CHECK_LAUNCH();
     return ok ? 0 : FCN_E_BADARG;
+}
+
+extern "C" int fcn_frustum_label_count(const float *frame_pts, const int64_t *frame_off, int F, int pt_stride, const double *P,
+                                       const double *V2C, const double *R0, const double *img_wh, const double *boxes,
+                                       const int32_t *box_frame, int D, int S, int clip_boxes, double clip_distance,
+                                       const double *gt_box3d, double *box2d, double *frustum_angle, int32_t *seg_cnt,
+                                       int32_t *seg_pos, double *corners, void *stream)
+{
+    return fl_count_launch(frame_pts, frame_off, F, pt_stride, P, V2C, R0, img_wh, boxes, box_frame, D, S, clip_boxes, clip_distance,
+                           gt_box3d, box2d, frustum_angle, seg_cnt, seg_pos, corners, stream, true);
+}
+
+extern "C" int fcn_frustum_label_fill(const float *frame_pts, const int64_t *frame_off, int F, int pt_stride, const double *P,
+                                      const double *V2C, const double *R0, const double *img_wh, const double *boxes,
+                                      const int32_t *box_frame, int D, int S, int clip_boxes, double clip_distance,
+                                      const double *gt_box3d, const int64_t *seg_off, float *out_pts, int64_t *out_seg,
+                                      void *stream)
+{
+    return fl_fill_launch(frame_pts, frame_off, F, pt_stride, P, V2C, R0, img_wh, boxes, box_frame, D, S, clip_boxes, clip_distance,
+                          gt_box3d, seg_off, out_pts, out_seg, stream, true);
 }

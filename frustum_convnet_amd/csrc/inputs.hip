@@ -473,3 +473,9 @@ extern "C" int fcn_prepare_inputs_refine(const fcn_inp_refine_desc *d, const flo
 // The random draws the prepare kernels above read -- resample indices, flip coin, depth-shift normal, height shift -- made on the
 // device by a counter-based generator (fcn_draw_batch, fcn_draw_limits): csrc/draws.h
 #include "draws.h"
+
+// ------------------------------------------------------------------------------------------------
+// The first stage's training input without a host read: box perturbation on the draws' stream, the labelled count / fill without
+// their read-back, and the one-workgroup plan between them (fcn_box2d_perturb, fcn_frustum_train_count / _plan / _fill):
+// csrc/frustum_plan.h
+#include "frustum_plan.h"

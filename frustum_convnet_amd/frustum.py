@@ -12,8 +12,13 @@ it once per detection on the host, pickling D ragged copies of the same frame fo
 kitti/prepare_data_refine.py:689-699 builds the rect-camera, image-FOV subset the refinement stage searches.  Here both are the
 same two HIP launches over a grid of (segments, boxes); the host reads the D * S segment counts between them (they size the
 point buffer) and each entry point reads box_frame and frame_off back to range-check them.  No point data crosses to the host.
+FrameTrainSource (at the end) is the KITTI training path again with NOTHING read back: frames and labels resident, boxes perturbed
+on the device, a one-workgroup plan in place of the host's kept list and prefix sum, a fixed batch size -- capturable
+(fcn_box2d_perturb, fcn_frustum_train_count / _plan / _fill, csrc/frustum_plan.h).
 No CPU fallback.
 """
+import ctypes
+
 import numpy as np
 import torch
 
@@ -395,3 +400,202 @@ def sunrgbd_training_candidates(frame_points, frame_off, K, Rtilt, boxes2d, box_
     return {"points": points, "seg": seg, "off": torch.cat([starts, soff[-1:]]), "box2d": pick(boxes.float().double()),
             "frustum_angle": pick(angle), "box3d": pick(corners), "heading": pick(gt[:, 6]), "size": pick(size),
             "box_frame": pick(bframe), "cnt": cnt, "pos": pos, "kept": kept, "counts": counts[kept], "sub": [sub[d] for d in kept]}
+
+
+# ------------------------------------------------------------------------------------------------
+# The KITTI first stage's training input as ONE capturable sequence of launches (csrc/frustum_plan.h)
+STATUS_BITS = ((1, "bit 0: a slot had no row to draw from (its choice row is zeros)"),
+               (2, "bit 1: fewer boxes survived than the batch has slots (the empty slots repeat box 0's labels over no rows)"),
+               (4, "bit 2: the selected rows exceed the capacity of the point buffer (the overflow was dropped)"),
+               (16, "bit 4: a box had no valid perturbation within the attempt cap (its label box was used as it is)"))
+
+
+class FrameTrainSource:
+    """Resident LiDAR frames and label boxes -> the InputBuilder training batch at a FIXED batch size B, every step, with no host
+    read and no upload: what perturb_boxes2d + frustum_training_candidates + InputBuilder.build_device_train(draws=DeviceDraws) do
+    behind three synchronisations, as one sequence of launches that can be captured into a hipGraph and draws anew on every replay
+    (INTEGRATION.md "Capturable first-stage training input" states the contract).
+    frame_points ... img_size as frustum_candidates takes them; gt_box2d (G,4), gt_box3d (G,7), box_frame (G), types (G names): the
+    G labels; builder: an InputBuilder (its npoints, strides, flip / shift); B: slots of the batch; D: labels tried per step
+    (B <= D <= G, D <= 2048); capacity: rows of the point buffer (rows beyond it are dropped and flagged); seed: the three
+    generators are DeviceDraws keyed seed (label pick), seed + 1 (box perturbation), seed + 2 (per-sample draws), each one step
+    further after every step().  pick=False: the first D labels in order; perturb=False: the boxes as they are -- select_box2d
+    (G,4) then optionally gives boxes that select in place of gt_box2d, which keeps deciding the reject rule.
+    Everything is validated here, once, on the host; step() validates nothing and reads nothing."""
+
+    def __init__(self, frame_points, frame_off, calib, img_size, gt_box2d, gt_box3d, box_frame, types, builder, B, D, capacity,
+                 seed, perturb=True, pick=True, shift_ratio=0.1, min_box_height=25.0, clip_distance=2.0, select_box2d=None):
+        from .inputs import DeviceDraws
+        who = "FrameTrainSource"
+        _need_cuda(frame_points, who)
+        dev = frame_points.device
+        L = _native.lib()
+        pts = frame_points.detach().contiguous().float()
+        if pts.dim() != 2 or pts.shape[1] < 3:
+            raise ValueError("%s: frame_points must be (n, >= 3), got %s" % (who, tuple(frame_points.shape)))
+        foff_h = torch.as_tensor(frame_off).detach().cpu().to(torch.int64).contiguous().view(-1).numpy()
+        F, ps = len(foff_h) - 1, int(pts.shape[1])
+        if F < 1 or foff_h[0] < 0 or (np.diff(foff_h) < 0).any() or foff_h[-1] > pts.shape[0]:
+            raise ValueError("%s: frame_off must be F + 1 >= 2 ascending row offsets into the %d rows" % (who, pts.shape[0]))
+        seg = int(L.fcn_frustum_select_seg())
+        S = max(1, -(-int(np.diff(foff_h).max()) // seg))       # no frame is longer than S segments: checked HERE, once
+        if pts.shape[0] == 0:
+            pts = torch.zeros((1, ps), dtype=torch.float32, device=dev)
+        P, V2C, R0, wh = _calib(calib, img_size, F, dev)
+        host = lambda a: (a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a))
+        gt2d = np.ascontiguousarray(host(gt_box2d), dtype=np.float64).reshape(-1, 4)
+        gt3d = np.ascontiguousarray(host(gt_box3d), dtype=np.float64).reshape(-1, 7)
+        bf = np.ascontiguousarray(host(box_frame)).reshape(-1)
+        G = len(bf)
+        types = [str(t) for t in types]
+        if len(gt2d) != G or len(gt3d) != G or len(types) != G:
+            raise ValueError("%s: %d box_frame, %d gt_box2d, %d gt_box3d, %d types" % (who, G, len(gt2d), len(gt3d), len(types)))
+        if bf.dtype.kind not in "iu" or G == 0 or int(bf.min()) < 0 or int(bf.max()) >= F:
+            raise ValueError("%s: box_frame must hold integers in [0, %d)" % (who, F))
+        B, D, capacity = int(B), int(D), int(capacity)
+        a, b = ctypes.c_int(0), ctypes.c_int(0)
+        _native.check(L.fcn_frustum_train_plan_limits(ctypes.byref(a), ctypes.byref(b)), "fcn_frustum_train_plan_limits")
+        max_d, max_segs = a.value, b.value
+        if not (1 <= B <= D <= G) or D > max_d:
+            raise ValueError("%s: need 1 <= B <= D <= G and D <= %d, got B = %d, D = %d, G = %d" % (who, max_d, B, D, G))
+        if D * S > max_segs:
+            raise ValueError("%s: D * S = %d * %d segments exceed the plan's %d" % (who, D, S, max_segs))
+        if capacity < 1:
+            raise ValueError("%s: capacity must be >= 1 row, got %d" % (who, capacity))
+        r = float(shift_ratio)
+        if not (0.0 <= r < 1.0):
+            raise ValueError("%s: shift_ratio must lie in [0, 1), got %r" % (who, shift_ratio))
+        bad = np.nonzero(~((gt2d[:, 0] < gt2d[:, 2]) & (gt2d[:, 1] < gt2d[:, 3])))[0]
+        if len(bad):
+            raise ValueError("%s: label box %d is degenerate: %r" % (who, bad[0], tuple(gt2d[bad[0]])))
+        wh_h = wh.cpu().numpy()[bf]
+        if perturb:                                             # perturb_boxes2d's second refusal, vectorised
+            if select_box2d is not None:
+                raise ValueError("%s: select_box2d goes with perturb=False" % who)
+            w, h = gt2d[:, 2] - gt2d[:, 0], gt2d[:, 3] - gt2d[:, 1]
+            cx, cy = (gt2d[:, 0] + gt2d[:, 2]) / 2.0, (gt2d[:, 1] + gt2d[:, 3]) / 2.0
+            rx, ry = w * r + w * (1 + r) / 2.0, h * r + h * (1 + r) / 2.0
+            bad = np.nonzero(~((cx - rx < wh_h[:, 0] - 1) & (cx + rx > 0) & (cy - ry < wh_h[:, 1] - 1) & (cy + ry > 0)))[0]
+            if len(bad):
+                raise ValueError("%s: label box %d cannot be perturbed into the %g x %g image: %r" %
+                                 (who, bad[0], wh_h[bad[0], 0], wh_h[bad[0], 1], tuple(gt2d[bad[0]])))
+        sel2d = gt2d if select_box2d is None else np.ascontiguousarray(host(select_box2d), dtype=np.float64).reshape(-1, 4)
+        if len(sel2d) != G:
+            raise ValueError("%s: %d select_box2d for %d labels" % (who, len(sel2d), G))
+        if builder.device.type != "cuda":
+            raise RuntimeError("frustum_convnet_amd: input construction is a HIP kernel (MI355X only); no CPU fallback")
+        cls = [builder.classes.index(t) if t in builder.classes else -1 for t in types]
+        if min(cls) < 0:
+            raise ValueError("%s: type %r is not one of %r" % (who, types[cls.index(-1)], tuple(builder.classes)))
+        self.device, self.builder = dev, builder
+        self.B, self.D, self.G, self.F, self.S, self.ps, self.capacity = B, D, G, F, S, ps, capacity
+        self.perturb, self.pick, self.shift_ratio = bool(perturb), bool(pick), r
+        self.min_box_height, self.clip_distance = float(min_box_height), float(clip_distance)
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+        f64, i32, i64 = (dict(dtype=t, device=dev) for t in (torch.float64, torch.int32, torch.int64))
+        N = builder.npoints
+        # ---- resident: the frames, the per-label tensors
+        self.frames = (pts, up(foff_h), P, V2C, R0, wh)
+        self.g_box2d, self.g_sel2d, self.g_box3d, self.g_frame = up(gt2d), up(sel2d), up(gt3d), up(bf.astype(np.int32))
+        self.g_heading, self.g_size = self.g_box3d[:, 6].contiguous(), self.g_box3d[:, 3:6].contiguous()
+        self.g_P = P.index_select(0, self.g_frame.to(torch.int64)).contiguous()
+        self.g_class = up(np.asarray(cls, dtype=np.int64).reshape(G, 1))
+        self.eye = torch.eye(len(builder.classes), dtype=torch.float32, device=dev)
+        self.g_count = torch.full((1,), G, **i64)
+        # ---- the generators
+        seed = int(seed)
+        self.draws_pick, self.draws_box, self.draws_sample = (DeviceDraws(seed + k, builder.device) for k in range(3))
+        self.status = torch.zeros((1,), **i32)
+        # ---- every intermediate
+        self.pick_idx = torch.arange(D, **i32).view(1, D)
+        self.pick_scalars = (torch.zeros((1,), **f64), torch.zeros((1,), **f64))
+        self.gt2d, self.sel2d, self.gt3d = torch.zeros((D, 4), **f64), torch.zeros((D, 4), **f64), torch.zeros((D, 7), **f64)
+        self.bframe = torch.zeros((D,), **i32)
+        self.boxes = torch.zeros((D, 4), **f64) if self.perturb else self.sel2d       # the boxes that select (perturbed or plain)
+        self.box2d, self.angle, self.corners = torch.zeros((D, 4), **f64), torch.zeros((D,), **f64), torch.zeros((D, 24), **f64)
+        self.both = torch.zeros((2, D, S), **i32)               # selected, positive
+        self.slot_box, self.n_kept = torch.zeros((B,), **i32), torch.zeros((1,), **i32)
+        self.seg_off, self.off = torch.zeros((D * S + 1,), **i64), torch.zeros((B + 1,), **i64)
+        # the spare row is what an empty slot's all-zero choice row reads: fcn_prepare_inputs indexes off[b] + choice
+        self.points = torch.zeros((capacity + 1, ps), dtype=torch.float32, device=dev)
+        self.seg = torch.zeros((capacity + 1,), **i64)
+        self.slot_label = torch.zeros((B,), **i32)
+        self.counts = torch.zeros((B,), **i64)
+        self.t = {"raw": self.points, "off": self.off, "seg": self.seg, "choice": torch.zeros((B, N), **i32),
+                  "fangle": torch.zeros((B,), **f64), "box2d": torch.zeros((B, 4), **f64), "P": torch.zeros((B, 12), **f64),
+                  "corners": torch.zeros((B, 24), **f64), "heading": torch.zeros((B,), **f64), "size": torch.zeros((B, 3), **f64),
+                  "coin": torch.zeros((B,), **f64), "normal": torch.zeros((B,), **f64),
+                  "size_class": torch.zeros((B, 1), **i64), "B": B, "pt_stride": ps}
+        if builder.one_hot:
+            self.t["one_hot"] = torch.zeros((B, len(builder.classes)), dtype=torch.float32, device=dev)
+        self.out = builder.alloc(B)
+        if not self.pick:                                       # the first D labels, gathered once
+            self._gather_labels()
+
+    @staticmethod
+    def limits():
+        """(the attempt cap of the perturbation, the largest D, the largest D * S) of the kernels."""
+        a, b, c = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
+        L = _native.lib()
+        _native.check(L.fcn_box2d_perturb_limits(ctypes.byref(a)), "fcn_box2d_perturb_limits")
+        _native.check(L.fcn_frustum_train_plan_limits(ctypes.byref(b), ctypes.byref(c)), "fcn_frustum_train_plan_limits")
+        return a.value, b.value, c.value
+
+    def _gather_labels(self):
+        idx = self.pick_idx.view(-1)
+        for src, dst in ((self.g_box2d, self.gt2d), (self.g_sel2d, self.sel2d), (self.g_box3d, self.gt3d), (self.g_frame, self.bframe)):
+            torch.index_select(src, 0, idx, out=dst)
+
+    def step(self):
+        """Enqueues one batch on the current stream -- pick, gather, perturb, count, plan, fill, gather, draw, fcn_prepare_inputs --
+        and nothing else: no allocation, no host read, no upload (capturable).  Returns the batch dict of InputBuilder.build(), same
+        keys, shapes and dtypes, at batch size B; the same tensors every step.  self.boxes (D,4) holds the step's perturbed boxes,
+        self.slot_box (B) the box of each slot, self.n_kept (1) the filled slots; check() reads the status words."""
+        L, dev, bld = _native.lib(), self.device, self.builder
+        B, D, S, t = self.B, self.D, self.S, self.t
+        p = lambda x: x.data_ptr()
+        pts, foff, P, V2C, R0, wh = self.frames
+        with torch.cuda.device(dev):
+            s = _native.current_stream(dev)
+            if self.pick:
+                self.draws_pick.draw(self.g_count, D, False, False, out=(self.pick_idx,) + self.pick_scalars)
+                self._gather_labels()
+            else:                                               # (the three step counters stay equal)
+                _native.check(L.fcn_box2d_perturb(p(self.gt2d), p(self.bframe), p(wh), 0, self.F, self.shift_ratio,
+                                                  self.draws_pick.seed, p(self.draws_pick.state), 1, p(self.gt2d), p(self.status), s),
+                              "fcn_box2d_perturb")
+            _native.check(L.fcn_box2d_perturb(p(self.gt2d), p(self.bframe), p(wh), D if self.perturb else 0, self.F, self.shift_ratio,
+                                              self.draws_box.seed, p(self.draws_box.state), 1, p(self.boxes), p(self.status), s),
+                          "fcn_box2d_perturb")
+            args = (p(pts), p(foff), self.F, self.ps, p(P), p(V2C), p(R0), p(wh), p(self.boxes), p(self.bframe), D, S, 0,
+                    self.clip_distance, p(self.gt3d))
+            _native.check(L.fcn_frustum_train_count(*args, p(self.box2d), p(self.angle), p(self.both[0]), p(self.both[1]),
+                                                    p(self.corners), s), "fcn_frustum_train_count")
+            _native.check(L.fcn_frustum_train_plan(p(self.both[0]), p(self.both[1]), p(self.gt2d), self.min_box_height, D, S, B,
+                                                   self.capacity, p(self.slot_box), p(self.seg_off), p(self.off), p(self.n_kept),
+                                                   p(self.status), s), "fcn_frustum_train_plan")
+            _native.check(L.fcn_frustum_train_fill(*args, p(self.seg_off), p(self.points), p(self.seg), s), "fcn_frustum_train_fill")
+            torch.index_select(self.pick_idx.view(-1), 0, self.slot_box, out=self.slot_label)
+            for src, dst in ((self.box2d, t["box2d"]), (self.angle, t["fangle"]), (self.corners, t["corners"])):
+                torch.index_select(src, 0, self.slot_box, out=dst)
+            for src, dst in ((self.g_heading, t["heading"]), (self.g_size, t["size"]), (self.g_P, t["P"]),
+                             (self.g_class, t["size_class"])):
+                torch.index_select(src, 0, self.slot_label, out=dst)
+            if "one_hot" in t:
+                torch.index_select(self.eye, 0, t["size_class"].view(-1), out=t["one_hot"])
+            torch.sub(self.off[1:], self.off[:-1], out=self.counts)
+            self.draws_sample.draw(self.counts, bld.npoints, bld.random_flip, bld.random_shift,
+                                   out=(t["choice"], t["coin"], t["normal"]))
+            return bld.launch(t, self.out)
+
+    def check(self):
+        """Reads the status words of the plan, the perturbation and the three generators (a synchronisation: not for a captured
+        region); raises ValueError naming the bits set since the last check() and clears them."""
+        words = (self.status, self.draws_pick.status, self.draws_box.status, self.draws_sample.status)
+        s = 0
+        for v in torch.cat(words).cpu().tolist():
+            s |= int(v)
+        if s:
+            for w in words:
+                w.zero_()
+            raise ValueError("FrameTrainSource: status %d -- %s" % (s, "; ".join(text for bit, text in STATUS_BITS if s & bit)))

@@ -788,6 +788,53 @@ int fcn_frustum_label_fill(const float *frame_pts, const int64_t *frame_off, int
                            const int64_t *seg_off, float *out_pts, int64_t *out_seg, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * The first stage's training input with no host read between its launches (csrc/frustum_plan.h; INTEGRATION.md "Capturable
+ * first-stage training input" states the contract bit for bit, tests/frustum_plan_ref.py restates it in numpy): perturb, count,
+ * plan, fill -- none of them reads anything back, allocates or synchronises, so the sequence can be captured into a hipGraph.
+ * Status bits (*status: one int32 on the device, OR-ed, never cleared here): bit 1 (2) fewer than B surviving boxes; bit 2 (4) rows
+ * dropped because the total exceeds `capacity`; bit 4 (16) a box fcn_box2d_perturb could not perturb.  (Bit 0 is fcn_draw_batch's.)
+ *
+ * fcn_box2d_perturb: kitti/prepare_data.py::random_shift_box2d (:55-77) for D boxes.  boxes (D,4) fp64 xmin ymin xmax ymax,
+ * box_frame (D) int32, img_wh (F,2) fp64 width, height; out (D,4) fp64.  Philox4x32-10 as fcn_draw_batch keys it, counter
+ * (block, d, step lo, ((step >> 32) << 2) | 3), step = state[0]: attempt t takes blocks 2t and 2t + 1 = words w0..w7, its four
+ * uniforms u(w0,w1), u(w2,w3), u(w4,w5), u(w6,w7), each * 2^-53, serve cx, cy, h, w in that order.  With r = shift_ratio,
+ * w = xmax - xmin, h = ymax - ymin, cx = (xmin + xmax) / 2, cy = (ymin + ymax) / 2, in fp64, one rounding per operation:
+ *   cx2 = cx + (w * r) * (u * 2 - 1), cy2 likewise with h; h2 = h * ((1 + (u * 2) * r) - r), w2 likewise with w;
+ *   x = fmin(fmax(cx2 -+ w2 / 2, 0), W - 1), y = fmin(fmax(cy2 -+ h2 / 2, 0), H - 1).
+ * The first attempt with xmin' < xmax' and ymin' < ymax' wins.  After fcn_box2d_perturb_limits' `attempts` (32) failed attempts,
+ * or when box_frame[d] is outside [0, F), out[d] = boxes[d] and bit 4 of *status is set: never silent, never unwritten.
+ * advance != 0: a one-thread launch behind the kernel leaves state[0] + 1.  NULL pointers, D < 0, F < 0 or shift_ratio outside
+ * [0, 1): FCN_E_BADARG, nothing written. */
+int fcn_box2d_perturb(const double *boxes, const int32_t *box_frame, const double *img_wh, int D, int F, double shift_ratio,
+                      uint64_t seed, const int64_t *state, int advance, double *out, int32_t *status, void *stream);
+int fcn_box2d_perturb_limits(int *attempts);
+/* fcn_frustum_label_count / _fill without the read-back of box_frame and frame_off: the same kernels, arguments, outputs and
+ * argument refusals.  A box whose frame is out of range is skipped as there (its counts are 0) but NOT reported, and "no frame is
+ * longer than S * fcn_frustum_select_seg() rows" is the caller's duty: rows beyond S segments would silently not be searched. */
+int fcn_frustum_train_count(const float *frame_pts, const int64_t *frame_off, int F, int pt_stride, const double *P,
+                            const double *V2C, const double *R0, const double *img_wh, const double *boxes,
+                            const int32_t *box_frame, int D, int S, int clip_boxes, double clip_distance, const double *gt_box3d,
+                            double *box2d, double *frustum_angle, int32_t *seg_cnt, int32_t *seg_pos, double *corners,
+                            void *stream);
+int fcn_frustum_train_fill(const float *frame_pts, const int64_t *frame_off, int F, int pt_stride, const double *P,
+                           const double *V2C, const double *R0, const double *img_wh, const double *boxes,
+                           const int32_t *box_frame, int D, int S, int clip_boxes, double clip_distance, const double *gt_box3d,
+                           const int64_t *seg_off, float *out_pts, int64_t *out_seg, void *stream);
+/* fcn_frustum_train_plan: what the host does between count and fill, as one workgroup.  seg_cnt, seg_pos (D,S) int32 from the
+ * count; gt_box2d (D,4) fp64 the unperturbed label boxes.  Box d survives iff not (gt_box2d[d,3] - gt_box2d[d,1] < min_box_height)
+ * and sum_s seg_pos[d,s] > 0.  The first B survivors in box order take slots 0..n-1: slot_box (B) int32 their box (0 for an empty
+ * slot), *n_kept = n.  seg_off (D*S+1) int64 = min(capacity, the exclusive prefix sum over the flattened segments of seg_cnt where
+ * the box holds a slot, else 0), the last entry the clamped total: what the fill takes, so a box without a slot writes nothing and
+ * rows beyond `capacity` are dropped (bit 2).  off (B+1) int64: off[i] = seg_off[slot_box[i] * S] for i < n, the clamped total
+ * from n on (an empty slot has no rows).  n < B sets bit 1.  Every output is written on every call.
+ * NULL pointers, D < 0, S < 1, B < 1, capacity < 0: FCN_E_BADARG; D or B > 2048 or D * S > 65536 (fcn_frustum_train_plan_limits):
+ * FCN_E_LIMIT; nothing written. */
+int fcn_frustum_train_plan(const int32_t *seg_cnt, const int32_t *seg_pos, const double *gt_box2d, double min_box_height, int D,
+                           int S, int B, int64_t capacity, int32_t *slot_box, int64_t *seg_off, int64_t *off, int32_t *n_kept,
+                           int32_t *status, void *stream);
+int fcn_frustum_train_plan_limits(int *max_d, int *max_segs);
+
+/* ---------------------------------------------------------------------------------------------
  * The SUN-RGBD front: upright-depth frames + per-frame K and Rtilt + 2-D boxes (+ one label 3-D box beside each) -> the raw
  * records fcn_prepare_inputs_sunrgbd(_infer) takes.  Replaces the host loops of sunrgbd/prepare_data.py::extract_frustum_data
  * (:132-267) and extract_frustum_data_from_rgb_detection (:270-381).  The grid, the segments (fcn_frustum_select_seg() rows), the
