@@ -225,6 +225,22 @@ CASES += [
     ("test_gpu_optim", "test_toy_state_transfer", ("sgd",)),
 ]
 
+# the ConvFeatNet kernels layer by layer off the fixture shapes (tests/fcn_ref.py): every case of the module
+import fcn_ref  # noqa: E402
+
+for _fn, _cases in (("test_train_case", fcn_ref.TRAIN_CASES), ("test_sentinel_rows", fcn_ref.SENTINEL_CASES),
+                    ("test_widths", fcn_ref.WIDTH_CASES), ("test_modes", fcn_ref.MODE_CASES)):
+    CASES += [("test_gpu_fcn_layers", _fn, (c.name, p)) for c in _cases for p in (fcn_ref.SPLIT, fcn_ref.F32)]
+CASES += [
+    ("test_gpu_fcn_layers", "test_second_run_on_the_same_workspace_is_bit_identical", ("plain_3x33",)),
+    ("test_gpu_fcn_layers", "test_second_run_on_the_same_workspace_is_bit_identical", ("base3_57x9",)),
+    ("test_gpu_fcn_layers", "test_prepacked_forward_is_bit_identical_to_the_inline_pack", ("plain_3x33",)),
+    ("test_gpu_fcn_layers", "test_prepacked_forward_is_bit_identical_to_the_inline_pack", ("frozen_base3_57x9",)),
+    ("test_gpu_fcn_layers", "test_running_logits_do_not_depend_on_the_rest_of_the_batch", (fcn_ref.SPLIT,)),
+    ("test_gpu_fcn_layers", "test_running_logits_do_not_depend_on_the_rest_of_the_batch", (fcn_ref.F32,)),
+    ("test_gpu_fcn_layers", "test_refusals_return_their_code_and_write_nothing", ()),
+]
+
 
 def _ident(c):
     a = c[2]
