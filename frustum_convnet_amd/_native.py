@@ -94,7 +94,9 @@ EXPORTS = ("fcn_arch", "fcn_build_hash", "fcn_stat_replicas", "fcn_query_depth_p
            "fcn_kitti_label_rows", "fcn_kitti_overlaps", "fcn_kitti_pass_a", "fcn_kitti_thresholds", "fcn_kitti_pass_b", "fcn_kitti_curves",
            "fcn_draw_batch", "fcn_draw_limits",
            "fcn_box2d_perturb", "fcn_box2d_perturb_limits", "fcn_frustum_train_count", "fcn_frustum_train_fill", "fcn_frustum_train_plan",
-           "fcn_frustum_train_plan_limits")
+           "fcn_frustum_train_plan_limits",
+           "fcn_box2d_perturb_sunrgbd", "fcn_frustum_sunrgbd_train_count", "fcn_frustum_sunrgbd_train_fill",
+           "fcn_frustum_sunrgbd_train_plan", "fcn_frustum_subsample_draw", "fcn_frustum_sunrgbd_train_slots", "fcn_draw_batch_sliced")
 
 _lib = None
 
@@ -300,6 +302,21 @@ def lib():
         L.fcn_frustum_train_plan.argtypes = [c_fp] * 3 + [ctypes.c_double] + [ctypes.c_int] * 3 + [ctypes.c_int64] + [c_fp] * 6
         L.fcn_frustum_train_plan_limits.restype = ctypes.c_int
         L.fcn_frustum_train_plan_limits.argtypes = [ctypes.POINTER(ctypes.c_int)] * 2
+    if hasattr(L, "fcn_frustum_sunrgbd_train_plan") or "FCN_LIB_NAME" not in os.environ:
+        L.fcn_box2d_perturb_sunrgbd.restype = ctypes.c_int
+        L.fcn_box2d_perturb_sunrgbd.argtypes = [c_fp, ctypes.c_int, ctypes.c_double, ctypes.c_uint64, c_fp, ctypes.c_int, c_fp, c_fp]
+        L.fcn_frustum_sunrgbd_train_count.restype = ctypes.c_int
+        L.fcn_frustum_sunrgbd_train_count.argtypes = sr_in + [c_fp] * 6
+        L.fcn_frustum_sunrgbd_train_fill.restype = ctypes.c_int
+        L.fcn_frustum_sunrgbd_train_fill.argtypes = sr_in + [c_fp] * 5
+        L.fcn_frustum_sunrgbd_train_plan.restype = ctypes.c_int
+        L.fcn_frustum_sunrgbd_train_plan.argtypes = [c_fp] * 2 + [ctypes.c_int] * 4 + [ctypes.c_int64] + [c_fp] * 6
+        L.fcn_frustum_subsample_draw.restype = ctypes.c_int
+        L.fcn_frustum_subsample_draw.argtypes = [c_fp] * 2 + [ctypes.c_int] * 2 + [ctypes.c_uint64, c_fp, ctypes.c_int] + [c_fp] * 3
+        L.fcn_frustum_sunrgbd_train_slots.restype = ctypes.c_int
+        L.fcn_frustum_sunrgbd_train_slots.argtypes = [c_fp] * 5 + [ctypes.c_int] * 4 + [ctypes.c_int64] + [c_fp] * 8
+        L.fcn_draw_batch_sliced.restype = ctypes.c_int
+        L.fcn_draw_batch_sliced.argtypes = [ctypes.POINTER(DrawDesc)] + [c_fp] * 4 + [ctypes.c_uint64] + [c_fp] * 7
     L.fcn_rotate_nms_3d.restype = ctypes.c_int
     L.fcn_rotate_nms_3d.argtypes = [c_fp] * 3 + [ctypes.c_int] * 3 + [ctypes.c_float, ctypes.c_int] + [c_fp] * 3
     _lib = L

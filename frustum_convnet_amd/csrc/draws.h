@@ -40,7 +40,16 @@ struct DrawArgs {
     int32_t *choice;
     double *coin, *normal, *hshift;
     int32_t *status;
+    // the two other forms of the same kernel (draw_batch_kernel's MODE)
+    const int64_t *slice_start = nullptr;  // DRAW_SLICED: row b's slice of sub is sub[slice_start[b] ..+ slice_len[b]) (B entries each,
+    const int32_t *slice_len = nullptr;    //              no packing assumed); slice_len[b] <= 0: no subsample
+    const int32_t *cnt32 = nullptr;        // DRAW_SUBSAMPLE: row b draws from cnt32[b] rows and writes choice[out_off[b] + i], i < N, only
+    const int64_t *out_off = nullptr;      //              where out_off[b + 1] > out_off[b]; no scalars
 };
+
+#define DRAW_ROWS 0                    // fcn_draw_batch: one row of choice per sample, subsample slices packed behind sub_off (B+1)
+#define DRAW_SLICED 1                  // fcn_draw_batch_sliced: the same, slices given as start + length per row
+#define DRAW_SUBSAMPLE 2               // fcn_frustum_subsample_draw: the frustum subsamples themselves (tag 0 only)
 
 // The high half of a 32 x 32 product is written as a 64-bit product's upper word: the host build of the tests has no __umulhi.
 __device__ __forceinline__ void draw_philox(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,
@@ -62,7 +71,7 @@ __device__ __forceinline__ double draw_u53(uint32_t hi, uint32_t lo)
     return (double)(hi >> 5) * 67108864.0 + (double)(lo >> 6);
 }
 
-template <int DIGIT_BITS, int SORT_CAP>
+template <int DIGIT_BITS, int SORT_CAP, int MODE = DRAW_ROWS>
 __global__ __launch_bounds__(DRAW_T) void draw_batch_kernel(DrawArgs a)
 {
     static_assert(SORT_CAP >= 2 && (SORT_CAP & (SORT_CAP - 1)) == 0, "the bitonic sort pads to a power of two");
@@ -78,7 +87,7 @@ __global__ __launch_bounds__(DRAW_T) void draw_batch_kernel(DrawArgs a)
     const uint32_t k0 = (uint32_t)a.seed, k1 = (uint32_t)(a.seed >> 32);
     uint32_t w[4];
 
-    if (tid == 0) {                                            // ---- the row's scalars (tag 2)
+    if (MODE != DRAW_SUBSAMPLE && tid == 0) {                  // ---- the row's scalars (tag 2)
         const double scale = 1.0 / 9007199254740992.0;         // 2^-53
         uint32_t v[4];
         draw_philox(0u, (uint32_t)b, c2, c3 | 2u, k0, k1, w);
@@ -94,13 +103,25 @@ __global__ __launch_bounds__(DRAW_T) void draw_batch_kernel(DrawArgs a)
         if (a.hshift) a.hshift[b] = hs;
     }
 
-    int64_t n64 = a.counts[b];
+    int64_t n64;
     const int32_t *sub = nullptr;
-    if (a.sub) {
-        const int64_t s0 = a.sub_off[b], s1 = a.sub_off[b + 1];
-        if (s1 > s0) { n64 = s1 - s0; sub = a.sub + s0; }
+    int32_t *row;
+    if constexpr (MODE == DRAW_SUBSAMPLE) {
+        const int64_t o0 = a.out_off[b];
+        if (a.out_off[b + 1] <= o0) return;                    // (workgroup-uniform) no subsample for this box
+        n64 = a.cnt32[b];
+        row = a.choice + o0;
+    } else {
+        n64 = a.counts[b];
+        if constexpr (MODE == DRAW_SLICED) {
+            const int32_t len = a.slice_len[b];
+            if (len > 0) { n64 = len; sub = a.sub + a.slice_start[b]; }
+        } else if (a.sub) {
+            const int64_t s0 = a.sub_off[b], s1 = a.sub_off[b + 1];
+            if (s1 > s0) { n64 = s1 - s0; sub = a.sub + s0; }
+        }
+        row = a.choice + (int64_t)b * N;
     }
-    int32_t *row = a.choice + (int64_t)b * N;
     if (n64 <= 0 || n64 >= 2147483648LL) {                     // ---- nothing to draw from: zeros (never unwritten) and the flag
         for (int c = tid; c < N; c += DRAW_T) row[c] = 0;
         if (tid == 0) atomicOr(a.status, 1);
@@ -242,15 +263,17 @@ static __global__ void draw_advance_kernel(int64_t *state)
     if (blockIdx.x == 0 && threadIdx.x == 0) state[0] = state[0] + 1;
 }
 
-template <int DIGIT_BITS, int SORT_CAP>
-static inline int draw_batch_launch(const DrawArgs &a, hipStream_t stream)
+template <int DIGIT_BITS, int SORT_CAP, int MODE = DRAW_ROWS>
+static inline int draw_batch_launch(const DrawArgs &a, hipStream_t stream, bool advance = true)
 {
     if (a.B <= 0 || a.N <= 0) return FCN_E_BADARG;
     if (a.N > SORT_CAP) return FCN_E_LIMIT;
-    hipLaunchKernelGGL((draw_batch_kernel<DIGIT_BITS, SORT_CAP>), dim3(a.B), dim3(DRAW_T), 0, stream, a);
+    hipLaunchKernelGGL((draw_batch_kernel<DIGIT_BITS, SORT_CAP, MODE>), dim3(a.B), dim3(DRAW_T), 0, stream, a);
     FCN_CHECK_LAUNCH();
-    hipLaunchKernelGGL(draw_advance_kernel, dim3(1), dim3(64), 0, stream, (int64_t *)a.state);
-    FCN_CHECK_LAUNCH();
+    if (advance) {
+        hipLaunchKernelGGL(draw_advance_kernel, dim3(1), dim3(64), 0, stream, (int64_t *)a.state);
+        FCN_CHECK_LAUNCH();
+    }
     return 0;
 }
 

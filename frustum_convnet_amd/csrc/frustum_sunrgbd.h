@@ -217,10 +217,16 @@ template <bool V4, bool LAB> __global__ __launch_bounds__(FS_T) void sr_fill_ker
 }
 
 // what the four entry points share: the refusals of frustum_select.h, then the launch.  count: scnt != nullptr
-static inline int sr_launch(SrArgs &a, bool fill, bool lab, hipStream_t stream)
+// read_lists: read box_frame and frame_off back first (fs_read_lists: a synchronisation) and report an out-of-range frame or a frame
+// longer than S segments; without it (the no-read pair of frustum_sunrgbd_plan.h) nothing is read and 0 is returned once the launch
+// is enqueued -- the kernels skip a box whose frame is out of range either way, the length condition is the caller's then.
+static inline int sr_launch(SrArgs &a, bool fill, bool lab, hipStream_t stream, bool read_lists = true)
 {
-    bool ok = false, fits = false;
-    FCN_TRY(fs_read_lists(a.bframe, a.foff, a.D, a.F, a.S, stream, &ok, &fits));
+    bool ok = true, fits = true;
+    if (read_lists) {
+        ok = false; fits = false;
+        FCN_TRY(fs_read_lists(a.bframe, a.foff, a.D, a.F, a.S, stream, &ok, &fits));
+    }
     if (!fits) return FCN_E_BADARG;
     const bool v4 = fs_vec4(a.pts, fill ? a.out : nullptr, a.ps);
     const dim3 grid(a.S, a.D), block(FS_T);
@@ -281,10 +287,12 @@ extern "C" int fcn_frustum_sunrgbd_fill(const float *frame_pts, const int64_t *f
     return sr_launch(a, true, false, (hipStream_t)stream);
 }
 
-extern "C" int fcn_frustum_sunrgbd_label_count(const float *frame_pts, const int64_t *frame_off, int F, int pt_stride,
-                                               const double *K, const double *Rtilt, const double *boxes, const int32_t *box_frame,
-                                               int D, int S, const double *gt_box3d, double *frustum_angle, int32_t *seg_cnt,
-                                               int32_t *seg_pos, double *corners, void *stream)
+// What the labelled entries below and the no-read pair of frustum_sunrgbd_plan.h (fcn_frustum_sunrgbd_train_count / _fill) share:
+// the argument checks, the kernels' arguments and the launch.
+static inline int sr_label_count_launch(const float *frame_pts, const int64_t *frame_off, int F, int pt_stride, const double *K,
+                                        const double *Rtilt, const double *boxes, const int32_t *box_frame, int D, int S,
+                                        const double *gt_box3d, double *frustum_angle, int32_t *seg_cnt, int32_t *seg_pos,
+                                        double *corners, void *stream, bool read_lists)
 {
     if (pt_stride < 3 || D < 0 || F < 0 || S < 1 || D > FS_MAX_D) return FCN_E_BADARG;
     if (D == 0) return 0;
@@ -299,13 +307,13 @@ extern "C" int fcn_frustum_sunrgbd_label_count(const float *frame_pts, const int
     SrArgs a;
     sr_args(a, frame_pts, frame_off, F, pt_stride, K, Rtilt, boxes, box_frame, D, S);
     a.gt = gt_box3d; a.angle = frustum_angle; a.scnt = seg_cnt; a.spos = seg_pos; a.corners = corners;
-    return sr_launch(a, false, true, (hipStream_t)stream);
+    return sr_launch(a, false, true, (hipStream_t)stream, read_lists);
 }
 
-extern "C" int fcn_frustum_sunrgbd_label_fill(const float *frame_pts, const int64_t *frame_off, int F, int pt_stride,
-                                              const double *K, const double *Rtilt, const double *boxes, const int32_t *box_frame,
-                                              int D, int S, const double *gt_box3d, const int64_t *seg_off, float *out_pts,
-                                              int64_t *out_seg, void *stream)
+static inline int sr_label_fill_launch(const float *frame_pts, const int64_t *frame_off, int F, int pt_stride, const double *K,
+                                       const double *Rtilt, const double *boxes, const int32_t *box_frame, int D, int S,
+                                       const double *gt_box3d, const int64_t *seg_off, float *out_pts, int64_t *out_seg,
+                                       void *stream, bool read_lists)
 {
     if (pt_stride < 3 || D < 0 || F < 0 || S < 1 || D > FS_MAX_D) return FCN_E_BADARG;
     if (D == 0 || F == 0) return 0;
@@ -314,7 +322,25 @@ extern "C" int fcn_frustum_sunrgbd_label_fill(const float *frame_pts, const int6
     SrArgs a;
     sr_args(a, frame_pts, frame_off, F, pt_stride, K, Rtilt, boxes, box_frame, D, S);
     a.gt = gt_box3d; a.soff = seg_off; a.out = out_pts; a.oseg = out_seg;
-    return sr_launch(a, true, true, (hipStream_t)stream);
+    return sr_launch(a, true, true, (hipStream_t)stream, read_lists);
+}
+
+extern "C" int fcn_frustum_sunrgbd_label_count(const float *frame_pts, const int64_t *frame_off, int F, int pt_stride,
+                                               const double *K, const double *Rtilt, const double *boxes, const int32_t *box_frame,
+                                               int D, int S, const double *gt_box3d, double *frustum_angle, int32_t *seg_cnt,
+                                               int32_t *seg_pos, double *corners, void *stream)
+{
+    return sr_label_count_launch(frame_pts, frame_off, F, pt_stride, K, Rtilt, boxes, box_frame, D, S, gt_box3d, frustum_angle, seg_cnt,
+                                 seg_pos, corners, stream, true);
+}
+
+extern "C" int fcn_frustum_sunrgbd_label_fill(const float *frame_pts, const int64_t *frame_off, int F, int pt_stride,
+                                              const double *K, const double *Rtilt, const double *boxes, const int32_t *box_frame,
+                                              int D, int S, const double *gt_box3d, const int64_t *seg_off, float *out_pts,
+                                              int64_t *out_seg, void *stream)
+{
+    return sr_label_fill_launch(frame_pts, frame_off, F, pt_stride, K, Rtilt, boxes, box_frame, D, S, gt_box3d, seg_off, out_pts,
+                                out_seg, stream, true);
 }
 
 // The positives a unit keeps after the reference's 2048-row subsample (prepare_data.py:219-226): pos[u] = the sum of

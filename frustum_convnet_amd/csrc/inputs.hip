@@ -479,3 +479,10 @@ extern "C" int fcn_prepare_inputs_refine(const fcn_inp_refine_desc *d, const flo
 // their read-back, and the one-workgroup plan between them (fcn_box2d_perturb, fcn_frustum_train_count / _plan / _fill):
 // csrc/frustum_plan.h
 #include "frustum_plan.h"
+
+// ------------------------------------------------------------------------------------------------
+// The SUN-RGBD training input without a host read: box perturbation, the labelled count / fill without their read-back, the
+// one-workgroup plan and slots kernels around the frustum subsample drawn on the device, and the draw with per-row subsample
+// slices (fcn_box2d_perturb_sunrgbd, fcn_frustum_sunrgbd_train_count / _plan / _fill / _slots, fcn_frustum_subsample_draw,
+// fcn_draw_batch_sliced): csrc/frustum_sunrgbd_plan.h
+#include "frustum_sunrgbd_plan.h"

@@ -14,7 +14,8 @@ same two HIP launches over a grid of (segments, boxes); the host reads the D * S
 point buffer) and each entry point reads box_frame and frame_off back to range-check them.  No point data crosses to the host.
 FrameTrainSource (at the end) is the KITTI training path again with NOTHING read back: frames and labels resident, boxes perturbed
 on the device, a one-workgroup plan in place of the host's kept list and prefix sum, a fixed batch size -- capturable
-(fcn_box2d_perturb, fcn_frustum_train_count / _plan / _fill, csrc/frustum_plan.h).
+(fcn_box2d_perturb, fcn_frustum_train_count / _plan / _fill, csrc/frustum_plan.h).  SunrgbdTrainSource is the same for the SUN-RGBD
+training path, with the frustum subsamples drawn on the device as well (csrc/frustum_sunrgbd_plan.h).
 No CPU fallback.
 """
 import ctypes
@@ -599,3 +600,236 @@ class FrameTrainSource:
             for w in words:
                 w.zero_()
             raise ValueError("FrameTrainSource: status %d -- %s" % (s, "; ".join(text for bit, text in STATUS_BITS if s & bit)))
+
+
+# ------------------------------------------------------------------------------------------------
+# The SUN-RGBD training input as ONE capturable sequence of launches (csrc/frustum_sunrgbd_plan.h)
+class SunrgbdTrainSource:
+    """Resident depth frames and label boxes -> the SunrgbdInputBuilder training batch at a FIXED batch size B, every step, with no
+    host read and no upload: what perturb_boxes2d_sunrgbd + sunrgbd_training_candidates (with its host rng.choice per large frustum)
+    + SunrgbdInputBuilder.build_device_train(draws=DeviceDraws) do behind four synchronisations, as one sequence of launches that
+    can be captured into a hipGraph and draws anew on every replay (INTEGRATION.md "Capturable SUN-RGBD training input" states the
+    contract).  It mirrors FrameTrainSource argument for argument: frame_points, frame_off as sunrgbd_candidates takes them; K, Rtilt
+    (F,3,3); gt_box2d (G,4), gt_box3d (G,7) in upright depth with HALF extents (as sunrgbd_training_candidates takes it), box_frame
+    (G), types (G names): the G labels; builder: a SunrgbdInputBuilder; B: slots of the batch; D: labels tried per step (B <= D <= G,
+    D <= 2048); capacity: rows of the point buffer; seed: four DeviceDraws keyed seed (label pick), seed + 1 (box perturbation),
+    seed + 2 (per-sample draws), seed + 3 (frustum subsamples), each one step further after every step(), whatever the options.
+    pick=False: the first D labels in order; perturb=False: the boxes as they are -- select_box2d (G,4) then optionally gives the
+    boxes that select; sub (with perturb=False and pick=False): one entry per first-D label, the subsample of that label's frustum
+    (indices into its selected rows) or None, in place of the device's draw -- range-checked here against the counts of one count
+    launch, and refused when `capacity` cannot hold every row (an index must never point at a row that was not stored).
+    ALL pre-kept boxes (full positives >= min_positives) are filled, not only the B that end up holding a slot: the slots are decided
+    after the subsample, which needs the labels of the stored rows.  So `capacity` has to hold the rows of up to D frustums:
+    D times the longest frame is a sure bound; a smaller buffer works as long as check() does not report bit 2 -- rows beyond it are
+    dropped (whole boxes from the end of the box order first) and every later count is the STORED count.
+    Everything is validated here, once, on the host; step() validates nothing, allocates nothing, reads nothing and uploads nothing."""
+
+    def __init__(self, frame_points, frame_off, K, Rtilt, gt_box2d, gt_box3d, box_frame, types, builder, B, D, capacity, seed,
+                 perturb=True, pick=True, shift_ratio=0.1, cap=SUNRGBD_CAP, min_positives=SUNRGBD_MIN, select_box2d=None, sub=None):
+        from .inputs import DeviceDraws
+        who = "SunrgbdTrainSource"
+        _need_cuda(frame_points, who)
+        dev = frame_points.device
+        L = _native.lib()
+        pts = frame_points.detach().contiguous().float()
+        if pts.dim() != 2 or pts.shape[1] < 3:
+            raise ValueError("%s: frame_points must be (n, >= 3), got %s" % (who, tuple(frame_points.shape)))
+        foff_h = torch.as_tensor(frame_off).detach().cpu().to(torch.int64).contiguous().view(-1).numpy()
+        F, ps = len(foff_h) - 1, int(pts.shape[1])
+        if F < 1 or foff_h[0] < 0 or (np.diff(foff_h) < 0).any() or foff_h[-1] > pts.shape[0]:
+            raise ValueError("%s: frame_off must be F + 1 >= 2 ascending row offsets into the %d rows" % (who, pts.shape[0]))
+        seg = int(L.fcn_frustum_select_seg())
+        S = max(1, -(-int(np.diff(foff_h).max()) // seg))       # no frame is longer than S segments: checked HERE, once
+        if pts.shape[0] == 0:
+            pts = torch.zeros((1, ps), dtype=torch.float32, device=dev)
+        cal = []
+        for name, m in (("K", K), ("Rtilt", Rtilt)):
+            t = torch.as_tensor(m).to(device=dev, dtype=torch.float64).contiguous()
+            if t.numel() != F * 9:
+                raise ValueError("%s: %s must hold %d x 9 numbers, got %s" % (who, name, F, tuple(t.shape)))
+            cal.append(t.view(F, 9))
+        host = lambda a: (a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a))
+        gt2d = np.ascontiguousarray(host(gt_box2d), dtype=np.float64).reshape(-1, 4)
+        gt3d = np.ascontiguousarray(host(gt_box3d), dtype=np.float64).reshape(-1, 7)
+        bf = np.ascontiguousarray(host(box_frame)).reshape(-1)
+        G = len(bf)
+        types = [str(t) for t in types]
+        if len(gt2d) != G or len(gt3d) != G or len(types) != G:
+            raise ValueError("%s: %d box_frame, %d gt_box2d, %d gt_box3d, %d types" % (who, G, len(gt2d), len(gt3d), len(types)))
+        if bf.dtype.kind not in "iu" or G == 0 or int(bf.min()) < 0 or int(bf.max()) >= F:
+            raise ValueError("%s: box_frame must hold integers in [0, %d)" % (who, F))
+        B, D, capacity, cap, min_positives = int(B), int(D), int(capacity), int(cap), int(min_positives)
+        max_d, max_segs, max_cap = self.limits()
+        if not (1 <= B <= D <= G) or D > max_d:
+            raise ValueError("%s: need 1 <= B <= D <= G and D <= %d, got B = %d, D = %d, G = %d" % (who, max_d, B, D, G))
+        if D * S > max_segs:
+            raise ValueError("%s: D * S = %d * %d segments exceed the plan's %d" % (who, D, S, max_segs))
+        if not (1 <= cap <= max_cap):
+            raise ValueError("%s: cap must lie in [1, %d], got %d" % (who, max_cap, cap))
+        if capacity < 1:
+            raise ValueError("%s: capacity must be >= 1 row, got %d" % (who, capacity))
+        r = float(shift_ratio)
+        if not (0.0 <= r < 1.0):
+            raise ValueError("%s: shift_ratio must lie in [0, 1), got %r" % (who, shift_ratio))
+        if perturb and select_box2d is not None:
+            raise ValueError("%s: select_box2d goes with perturb=False" % who)
+        if sub is not None and (perturb or pick):
+            raise ValueError("%s: sub goes with perturb=False and pick=False" % who)
+        sel2d = gt2d if select_box2d is None else np.ascontiguousarray(host(select_box2d), dtype=np.float64).reshape(-1, 4)
+        if len(sel2d) != G:
+            raise ValueError("%s: %d select_box2d for %d labels" % (who, len(sel2d), G))
+        if builder.device.type != "cuda":
+            raise RuntimeError("frustum_convnet_amd: input construction is a HIP kernel (MI355X only); no CPU fallback")
+        cls = [builder.classes.index(t) if t in builder.classes else -1 for t in types]
+        if min(cls) < 0:
+            raise ValueError("%s: type %r is not one of %r" % (who, types[cls.index(-1)], tuple(builder.classes)))
+        self.device, self.builder = dev, builder
+        self.B, self.D, self.G, self.F, self.S, self.ps, self.capacity = B, D, G, F, S, ps, capacity
+        self.perturb, self.pick, self.shift_ratio, self.cap, self.min_positives = bool(perturb), bool(pick), r, cap, min_positives
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+        f64, i32, i64 = (dict(dtype=t, device=dev) for t in (torch.float64, torch.int32, torch.int64))
+        N = builder.npoints
+        # ---- resident: the frames, the per-label tensors
+        self.frames = (pts, up(foff_h), cal[0], cal[1])
+        self.g_box2d, self.g_sel2d, self.g_box3d, self.g_frame = up(gt2d), up(sel2d), up(gt3d), up(bf.astype(np.int32))
+        self.g_heading = self.g_box3d[:, 6].contiguous()
+        self.g_size = (self.g_box3d[:, 3:6] * 2.0).contiguous()                 # box3d_size = 2l, 2w, 2h
+        self.g_K = cal[0].index_select(0, self.g_frame.to(torch.int64)).contiguous()
+        self.g_R = cal[1].index_select(0, self.g_frame.to(torch.int64)).contiguous()
+        self.g_class = up(np.asarray(cls, dtype=np.int64).reshape(G, 1))
+        self.eye = torch.eye(len(builder.classes), dtype=torch.float32, device=dev)
+        self.g_count = torch.full((1,), G, **i64)
+        # ---- the generators
+        seed = int(seed)
+        self.draws_pick, self.draws_box, self.draws_sample, self.draws_sub = (DeviceDraws(seed + k, builder.device) for k in range(4))
+        self.status = torch.zeros((1,), **i32)
+        # ---- every intermediate
+        self.pick_idx = torch.arange(D, **i32).view(1, D)
+        self.pick_scalars = (torch.zeros((1,), **f64), torch.zeros((1,), **f64))
+        self.gt2d, self.sel2d, self.gt3d = torch.zeros((D, 4), **f64), torch.zeros((D, 4), **f64), torch.zeros((D, 7), **f64)
+        self.bframe = torch.zeros((D,), **i32)
+        self.boxes = torch.zeros((D, 4), **f64) if self.perturb else self.sel2d       # the boxes that select (perturbed or plain)
+        self.box32, self.box64 = torch.zeros((D, 4), dtype=torch.float32, device=dev), torch.zeros((D, 4), **f64)
+        self.angle, self.corners = torch.zeros((D,), **f64), torch.zeros((D, 24), **f64)
+        self.both = torch.zeros((2, D, S), **i32)               # selected, positive
+        self.seg_off, self.row0 = torch.zeros((D * S + 1,), **i64), torch.zeros((D,), **i64)
+        self.cnt_stored, self.pos = torch.zeros((D,), **i32), torch.zeros((D,), **i32)
+        self.plan_sub_off = torch.zeros((D + 1,), **i64)
+        self.sub_off, self.sub = self.plan_sub_off, torch.zeros((D * cap,), **i32)
+        self.fixed_sub = sub is not None
+        # the spare row is what an empty slot's all-zero choice row reads: fcn_prepare_inputs_sunrgbd indexes off[b] + choice
+        self.points = torch.zeros((capacity + 1, ps), dtype=torch.float32, device=dev)
+        self.seg = torch.zeros((capacity + 1,), **i64)
+        self.slot_box, self.n_kept, self.slot_label = torch.zeros((B,), **i32), torch.zeros((1,), **i32), torch.zeros((B,), **i32)
+        self.off, self.counts, self.sub_start = torch.zeros((B,), **i64), torch.zeros((B,), **i64), torch.zeros((B,), **i64)
+        self.sub_len = torch.zeros((B,), **i32)
+        self.t = {"raw": self.points, "off": self.off, "seg": self.seg, "choice": torch.zeros((B, N), **i32),
+                  "fangle": torch.zeros((B,), **f64), "box2d": torch.zeros((B, 4), **f64), "K": torch.zeros((B, 9), **f64),
+                  "R": torch.zeros((B, 9), **f64), "corners": torch.zeros((B, 24), **f64), "heading": torch.zeros((B,), **f64),
+                  "size": torch.zeros((B, 3), **f64), "coin": torch.zeros((B,), **f64), "normal": torch.zeros((B,), **f64),
+                  "hshift": torch.zeros((B,), **f64), "size_class": torch.zeros((B, 1), **i64), "B": B, "pt_stride": ps}
+        if builder.one_hot:
+            self.t["one_hot"] = torch.zeros((B, len(builder.classes)), dtype=torch.float32, device=dev)
+        self.out = builder.alloc(B)
+        if not self.pick:                                       # the first D labels, gathered once
+            self._gather_labels()
+        if self.fixed_sub:                                      # one count launch, read once: what the table is checked against
+            with torch.cuda.device(dev):
+                _native.check(L.fcn_frustum_sunrgbd_train_count(*self._args(), self.angle.data_ptr(), self.both[0].data_ptr(),
+                                                                self.both[1].data_ptr(), self.corners.data_ptr(),
+                                                                _native.current_stream(dev)), "fcn_frustum_sunrgbd_train_count")
+            both_h = self.both.cpu().numpy().astype(np.int64)
+            counts = both_h[0].sum(1)
+            sub = _check_sub(who, list(sub), counts)
+            rows = int(counts[both_h[1].sum(1) >= min_positives].sum())
+            if rows > capacity:
+                raise ValueError("%s: sub needs a capacity that holds every row of the pre-kept boxes: %d > %d" % (who, rows, capacity))
+            lens = [0 if ix is None else len(ix) for ix in sub]
+            flat = [ix for ix in sub if ix is not None]
+            self.sub_off = up(np.concatenate([[0], np.cumsum(lens)]).astype(np.int64))
+            self.sub = up(np.concatenate(flat).astype(np.int32)) if flat else torch.zeros((1,), **i32)
+
+    @staticmethod
+    def limits():
+        """(the largest D, the largest D * S, the largest cap) of the kernels."""
+        a, b, c, d = (ctypes.c_int(0) for _ in range(4))
+        L = _native.lib()
+        _native.check(L.fcn_frustum_train_plan_limits(ctypes.byref(a), ctypes.byref(b)), "fcn_frustum_train_plan_limits")
+        _native.check(L.fcn_draw_limits(ctypes.byref(c), ctypes.byref(d)), "fcn_draw_limits")
+        return a.value, b.value, c.value
+
+    def _gather_labels(self):
+        idx = self.pick_idx.view(-1)
+        for src, dst in ((self.g_box2d, self.gt2d), (self.g_sel2d, self.sel2d), (self.g_box3d, self.gt3d), (self.g_frame, self.bframe)):
+            torch.index_select(src, 0, idx, out=dst)
+
+    def _args(self):
+        pts, foff, K, R = self.frames
+        return (pts.data_ptr(), foff.data_ptr(), self.F, self.ps, K.data_ptr(), R.data_ptr(), self.boxes.data_ptr(),
+                self.bframe.data_ptr(), self.D, self.S, self.gt3d.data_ptr())
+
+    def step(self):
+        """Enqueues one batch on the current stream -- pick, gather, perturb, count, plan, fill, subsample, fcn_frustum_subset_pos,
+        slots, gather, draw, fcn_prepare_inputs_sunrgbd -- and nothing else: no allocation, no host read, no upload (capturable).
+        Returns the batch dict of SunrgbdInputBuilder.build(), same keys, shapes and dtypes, at batch size B; the same tensors every
+        step.  self.boxes (D,4) holds the step's boxes, self.sub / self.sub_off the subsample table, self.slot_box (B) the box of
+        each slot, self.n_kept (1) the filled slots; check() reads the status words."""
+        L, dev, bld = _native.lib(), self.device, self.builder
+        B, D, S, t = self.B, self.D, self.S, self.t
+        p = lambda x: x.data_ptr()
+        with torch.cuda.device(dev):
+            s = _native.current_stream(dev)
+            if self.pick:
+                self.draws_pick.draw(self.g_count, D, False, False, out=(self.pick_idx,) + self.pick_scalars)
+                self._gather_labels()
+            else:                                               # (the four step counters stay equal)
+                _native.check(L.fcn_box2d_perturb_sunrgbd(p(self.gt2d), 0, self.shift_ratio, self.draws_pick.seed,
+                                                          p(self.draws_pick.state), 1, p(self.gt2d), s), "fcn_box2d_perturb_sunrgbd")
+            _native.check(L.fcn_box2d_perturb_sunrgbd(p(self.gt2d), D if self.perturb else 0, self.shift_ratio, self.draws_box.seed,
+                                                      p(self.draws_box.state), 1, p(self.boxes), s), "fcn_box2d_perturb_sunrgbd")
+            args = self._args()
+            _native.check(L.fcn_frustum_sunrgbd_train_count(*args, p(self.angle), p(self.both[0]), p(self.both[1]), p(self.corners), s),
+                          "fcn_frustum_sunrgbd_train_count")
+            _native.check(L.fcn_frustum_sunrgbd_train_plan(p(self.both[0]), p(self.both[1]), self.min_positives, self.cap, D, S,
+                                                           self.capacity, p(self.seg_off), p(self.row0), p(self.cnt_stored),
+                                                           p(self.plan_sub_off), p(self.status), s), "fcn_frustum_sunrgbd_train_plan")
+            _native.check(L.fcn_frustum_sunrgbd_train_fill(*args, p(self.seg_off), p(self.points), p(self.seg), s),
+                          "fcn_frustum_sunrgbd_train_fill")
+            _native.check(L.fcn_frustum_subsample_draw(p(self.cnt_stored), p(self.plan_sub_off), 0 if self.fixed_sub else D, self.cap,
+                                                       self.draws_sub.seed, p(self.draws_sub.state), 1, p(self.sub),
+                                                       p(self.draws_sub.status), s), "fcn_frustum_subsample_draw")
+            _native.check(L.fcn_frustum_subset_pos(p(self.seg), p(self.row0), p(self.cnt_stored), p(self.sub), p(self.sub_off), D,
+                                                   p(self.pos), s), "fcn_frustum_subset_pos")
+            _native.check(L.fcn_frustum_sunrgbd_train_slots(p(self.both[1]), p(self.pos), p(self.row0), p(self.cnt_stored),
+                                                            p(self.sub_off), self.min_positives, D, S, B, self.capacity,
+                                                            p(self.slot_box), p(self.n_kept), p(self.off), p(self.counts),
+                                                            p(self.sub_start), p(self.sub_len), p(self.status), s),
+                          "fcn_frustum_sunrgbd_train_slots")
+            torch.index_select(self.pick_idx.view(-1), 0, self.slot_box, out=self.slot_label)
+            self.box32.copy_(self.boxes)                        # the float32 value the reference records, widened again
+            self.box64.copy_(self.box32)
+            for src, dst in ((self.box64, t["box2d"]), (self.angle, t["fangle"]), (self.corners, t["corners"])):
+                torch.index_select(src, 0, self.slot_box, out=dst)
+            for src, dst in ((self.g_heading, t["heading"]), (self.g_size, t["size"]), (self.g_K, t["K"]), (self.g_R, t["R"]),
+                             (self.g_class, t["size_class"])):
+                torch.index_select(src, 0, self.slot_label, out=dst)
+            if "one_hot" in t:
+                torch.index_select(self.eye, 0, t["size_class"].view(-1), out=t["one_hot"])
+            dd = self.draws_sample
+            desc = _native.DrawDesc(B, bld.npoints, 1 if bld.random_flip else 0, 1 if bld.random_shift else 0)
+            _native.check(L.fcn_draw_batch_sliced(ctypes.byref(desc), p(self.counts), p(self.sub), p(self.sub_start), p(self.sub_len),
+                                                  dd.seed, p(dd.state), p(t["choice"]), p(t["coin"]), p(t["normal"]), p(t["hshift"]),
+                                                  p(dd.status), s), "fcn_draw_batch_sliced")
+            return bld.launch(t, self.out)
+
+    def check(self):
+        """Reads the status words of the plan, the slots and the four generators (a synchronisation: not for a captured region);
+        raises ValueError naming the bits set since the last check() and clears them."""
+        words = (self.status, self.draws_pick.status, self.draws_box.status, self.draws_sample.status, self.draws_sub.status)
+        s = 0
+        for v in torch.cat(words).cpu().tolist():
+            s |= int(v)
+        if s:
+            for w in words:
+                w.zero_()
+            raise ValueError("SunrgbdTrainSource: status %d -- %s" % (s, "; ".join(text for bit, text in STATUS_BITS if s & bit)))

@@ -377,9 +377,23 @@ class SunrgbdInputBuilder:
         if isinstance(draws, DeviceDraws):
             draws = draws.draw(_row_counts(t["off"]), N, self.random_flip, self.random_shift, hshift=True)
         t["choice"], t["coin"], t["normal"], t["hshift"] = _draw_tensors(draws, dev, 4)
-        seg_raw = None
-        if with_seg:
-            seg_raw = up(np.concatenate([np.asarray(r["seg"]).astype(np.int64) for r in records], 0))
+        t["seg"] = up(np.concatenate([np.asarray(r["seg"]).astype(np.int64) for r in records], 0)) if with_seg else None
+        self._classes(t, [self.classes.index(r["type"]) for r in records])
+        t["B"], t["pt_stride"] = B, stride
+        return self.launch(t)
+
+    def _classes(self, t, size_class):
+        """size_class (B,1) int64 and, with one_hot, its one-hot rows from a host list of class indices, uploaded into t."""
+        B = len(size_class)
+        t["size_class"] = torch.tensor(size_class, dtype=torch.int64).view(B, 1).to(self.device, non_blocking=True)
+        if self.one_hot:
+            oh = np.zeros((B, len(self.classes)), dtype=np.float32)
+            oh[np.arange(B), size_class] = 1.0
+            t["one_hot"] = torch.from_numpy(oh).to(self.device, non_blocking=True)
+
+    def alloc(self, B, with_seg=True):
+        """Output tensors of launch() for a batch of B frustums (pass as `out` to write the same buffers every step)."""
+        dev, N = self.device, self.npoints
         f32 = dict(dtype=torch.float32, device=dev)
         out = {"point_cloud": torch.empty((B, 3, N), **f32), "rot_angle": torch.empty((B, 1), **f32),
                "cls_label": torch.empty((B, self.L[1]), dtype=torch.int64, device=dev),
@@ -389,28 +403,35 @@ class SunrgbdInputBuilder:
             out["center_ref%d" % (s + 1)] = torch.empty((B, 3, self.L[s]), **f32)
         if with_seg:
             out["seg_label"] = torch.empty((B, N), dtype=torch.int64, device=dev)
-        desc = Inp5Desc(B, N, stride, (ctypes.c_int32 * 5)(*self.L), (ctypes.c_double * 5)(*self.strides), self.max_depth,
+        return out
+
+    def launch(self, t, out=None):
+        """ONE kernel launch on the current stream: device tensors `t` -- raw, off, seg (or None), choice, fangle, box2d, K, R,
+        corners, heading, size, coin, normal, hshift, size_class (, one_hot), B, pt_stride -- -> the batch dict (into `out` when
+        given: capturable into a hipGraph, no allocation, no host work besides the call).  size_class / one_hot are t's tensors."""
+        B, N = t["B"], self.npoints
+        dev = self.device
+        if out is None:
+            out = self.alloc(B, with_seg=t["seg"] is not None)
+        desc = Inp5Desc(B, N, t["pt_stride"], (ctypes.c_int32 * 5)(*self.L), (ctypes.c_double * 5)(*self.strides), self.max_depth,
                         1 if self.random_flip else 0, 1 if self.random_shift else 0)
         refs = (ctypes.c_void_p * 5)(*[out["center_ref%d" % (s + 1)].data_ptr() for s in range(5)])
         p = lambda x: None if x is None else x.data_ptr()
-        L = _native.lib()
         with torch.cuda.device(dev):
-            _native.check(L.fcn_prepare_inputs_sunrgbd(
-                ctypes.byref(desc), p(t["raw"]), p(t["off"]), p(seg_raw), p(t["choice"]), p(t["fangle"]), p(t["box2d"]),
+            _native.check(_native.lib().fcn_prepare_inputs_sunrgbd(
+                ctypes.byref(desc), p(t["raw"]), p(t["off"]), p(t["seg"]), p(t["choice"]), p(t["fangle"]), p(t["box2d"]),
                 p(t["K"]), p(t["R"]), p(t["corners"]), p(t["heading"]), p(t["size"]), p(t["coin"]), p(t["normal"]),
                 p(t["hshift"]), p(out["point_cloud"]), refs, p(out["cls_label"]), p(out["box3d_center"]),
-                p(out["box3d_heading"]), p(out["box3d_size"]), p(out["rot_angle"]), p(out.get("seg_label")),
+                p(out["box3d_heading"]), p(out["box3d_size"]), p(out["rot_angle"]),
+                p(out.get("seg_label")) if t["seg"] is not None else None,
                 _native.current_stream(dev)), "fcn_prepare_inputs_sunrgbd")
-        for v in t.values():
-            v.record_stream(torch.cuda.current_stream(dev))
-        size_class = [self.classes.index(r["type"]) for r in records]
-        out["size_class"] = torch.tensor(size_class, dtype=torch.int64).view(B, 1).to(dev, non_blocking=True)
-        if self.one_hot:
-            oh = np.zeros((B, len(self.classes)), dtype=np.float32)
-            oh[np.arange(B), size_class] = 1.0
-            out["one_hot"] = up(oh)
+        for v in t.values():                       # the uploads are read by the kernel just enqueued
+            if isinstance(v, torch.Tensor):
+                v.record_stream(torch.cuda.current_stream(dev))
+        out["size_class"] = t["size_class"]
+        if "one_hot" in t:
+            out["one_hot"] = t["one_hot"]
         return out
-
 
     def _compose(self, choice, sub):
         """The builder's draw through the reference's frustum subsample: choice (B,N) indexes the subsampled record where a box
@@ -523,41 +544,13 @@ class SunrgbdInputBuilder:
         if isinstance(draws, DeviceDraws):
             draws = self._device_draw(draws, sel["cnt"], sel["sub"], self.random_flip, self.random_shift)
         coin, normal, hshift = _draw_tensors(draws, dev, 4)[1:]
-        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev, non_blocking=True)
         Kd, Rd = self._calib_rows(K, Rtilt, sel["box_frame"])
-        t = {"raw": sel["points"], "off": sel["off"], "choice": self._choice(draws, sel["sub"]), "fangle": sel["frustum_angle"],
-             "box2d": sel["box2d"], "K": Kd, "R": Rd, "corners": sel["box3d"].reshape(B, 24), "heading": sel["heading"],
-             "size": sel["size"], "coin": coin, "normal": normal, "hshift": hshift}
-        seg_raw = sel["seg"] if with_seg else None
-        f32 = dict(dtype=torch.float32, device=dev)
-        out = {"point_cloud": torch.empty((B, 3, N), **f32), "rot_angle": torch.empty((B, 1), **f32),
-               "cls_label": torch.empty((B, self.L[1]), dtype=torch.int64, device=dev),
-               "box3d_center": torch.empty((B, 3), **f32), "box3d_heading": torch.empty((B, 1), **f32),
-               "box3d_size": torch.empty((B, 3), **f32)}
-        for s in range(5):
-            out["center_ref%d" % (s + 1)] = torch.empty((B, 3, self.L[s]), **f32)
-        if with_seg:
-            out["seg_label"] = torch.empty((B, N), dtype=torch.int64, device=dev)
-        desc = Inp5Desc(B, N, int(sel["points"].shape[1]), (ctypes.c_int32 * 5)(*self.L), (ctypes.c_double * 5)(*self.strides),
-                        self.max_depth, 1 if self.random_flip else 0, 1 if self.random_shift else 0)
-        refs = (ctypes.c_void_p * 5)(*[out["center_ref%d" % (s + 1)].data_ptr() for s in range(5)])
-        p = lambda x: None if x is None else x.data_ptr()
-        with torch.cuda.device(dev):
-            _native.check(_native.lib().fcn_prepare_inputs_sunrgbd(
-                ctypes.byref(desc), p(t["raw"]), p(t["off"]), p(seg_raw), p(t["choice"]), p(t["fangle"]), p(t["box2d"]),
-                p(t["K"]), p(t["R"]), p(t["corners"]), p(t["heading"]), p(t["size"]), p(t["coin"]), p(t["normal"]),
-                p(t["hshift"]), p(out["point_cloud"]), refs, p(out["cls_label"]), p(out["box3d_center"]),
-                p(out["box3d_heading"]), p(out["box3d_size"]), p(out["rot_angle"]), p(out.get("seg_label")),
-                _native.current_stream(dev)), "fcn_prepare_inputs_sunrgbd")
-        for v in list(t.values()) + ([seg_raw] if with_seg else []):
-            v.record_stream(torch.cuda.current_stream(dev))
-        size_class = [self.classes.index(types[i]) for i in kept]
-        out["size_class"] = torch.tensor(size_class, dtype=torch.int64).view(B, 1).to(dev, non_blocking=True)
-        if self.one_hot:
-            oh = np.zeros((B, len(self.classes)), dtype=np.float32)
-            oh[np.arange(B), size_class] = 1.0
-            out["one_hot"] = up(oh)
-        return out
+        t = {"raw": sel["points"], "off": sel["off"], "seg": sel["seg"] if with_seg else None, "choice": self._choice(draws, sel["sub"]),
+             "fangle": sel["frustum_angle"], "box2d": sel["box2d"], "K": Kd, "R": Rd, "corners": sel["box3d"].reshape(B, 24),
+             "heading": sel["heading"], "size": sel["size"], "coin": coin, "normal": normal, "hshift": hshift}
+        self._classes(t, [self.classes.index(types[i]) for i in kept])
+        t["B"], t["pt_stride"] = B, int(sel["points"].shape[1])
+        return self.launch(t)
 
 
 def sunrgbd_records_from_fixture(g):

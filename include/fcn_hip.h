@@ -882,6 +882,73 @@ int fcn_frustum_subset_pos(const int64_t *seg, const int64_t *off, const int32_t
                            int U, int32_t *pos, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * The SUN-RGBD training input with no host read between its launches (csrc/frustum_sunrgbd_plan.h; INTEGRATION.md "Capturable
+ * SUN-RGBD training input" states the contract bit for bit, tests/sunrgbd_plan_ref.py restates it in numpy): perturb, count, plan,
+ * fill, subsample, fcn_frustum_subset_pos, slots, sliced draw -- none of them reads anything back, allocates or synchronises, so the
+ * sequence can be captured into a hipGraph.  Status bits (*status: one int32 on the device, OR-ed, never cleared here): bit 1 (2)
+ * fewer than B surviving boxes; bit 2 (4) rows dropped because the total exceeds `capacity`.  Bit 0 is the draws'; bit 4 is never set.
+ *
+ * fcn_box2d_perturb_sunrgbd: sunrgbd/sunrgbd_utils.py::random_shift_box2d (:208-221) for D boxes, no clip, no retry.  boxes, out
+ * (D,4) fp64 xmin ymin xmax ymax.  The stream is fcn_box2d_perturb's: Philox4x32-10, counter (block, d, step lo,
+ * ((step >> 32) << 2) | 3), step = state[0], blocks 0 and 1 = words w0..w7; the four uniforms u(w0,w1), u(w2,w3), u(w4,w5), u(w6,w7),
+ * each * 2^-53, serve cx, cy, h, w in that order.  With r = shift_ratio, w = xmax - xmin, h = ymax - ymin, cx = (xmin + xmax) / 2,
+ * cy = (ymin + ymax) / 2, in fp64, one rounding per operation:
+ *   cx2 = cx + (w * r) * (u * 2 - 1), cy2 likewise with h; h2 = h * ((1 + (u * 2) * r) - r), w2 likewise with w;
+ *   out = cx2 - w2 / 2, cy2 - h2 / 2, cx2 + w2 / 2, cy2 + h2 / 2.
+ * D == 0: the pass-through (nothing written).  advance != 0: a one-thread launch behind the kernel leaves state[0] + 1.
+ * NULL pointers, D < 0 or shift_ratio outside [0, 1): FCN_E_BADARG, nothing written. */
+int fcn_box2d_perturb_sunrgbd(const double *boxes, int D, double shift_ratio, uint64_t seed, const int64_t *state, int advance,
+                              double *out, void *stream);
+/* fcn_frustum_sunrgbd_label_count / _fill without the read-back of box_frame and frame_off: the same kernels, arguments, outputs and
+ * argument refusals.  A box whose frame is out of range is skipped as there (its counts are 0) but NOT reported, and "no frame is
+ * longer than S * fcn_frustum_select_seg() rows" is the caller's duty: rows beyond S segments would silently not be searched. */
+int fcn_frustum_sunrgbd_train_count(const float *frame_pts, const int64_t *frame_off, int F, int pt_stride, const double *K,
+                                    const double *Rtilt, const double *boxes, const int32_t *box_frame, int D, int S,
+                                    const double *gt_box3d, double *frustum_angle, int32_t *seg_cnt, int32_t *seg_pos,
+                                    double *corners, void *stream);
+int fcn_frustum_sunrgbd_train_fill(const float *frame_pts, const int64_t *frame_off, int F, int pt_stride, const double *K,
+                                   const double *Rtilt, const double *boxes, const int32_t *box_frame, int D, int S,
+                                   const double *gt_box3d, const int64_t *seg_off, float *out_pts, int64_t *out_seg, void *stream);
+/* fcn_frustum_sunrgbd_train_plan: what the host does between count and fill, as one workgroup.  seg_cnt, seg_pos (D,S) int32 from
+ * the count.  Box d is PRE-KEPT iff sum_s seg_pos[d,s] >= min_positives.  seg_off (D*S+1) int64 = min(capacity, the exclusive prefix
+ * sum over the flattened segments of seg_cnt where the box is pre-kept, else 0), the last entry the clamped total: what the fill
+ * takes, so a dropped box writes nothing and rows beyond `capacity` are dropped (bit 2).  row0 (D) int64 = seg_off[d * S].
+ * cnt_stored (D) int32 = seg_off[(d + 1) * S] - seg_off[d * S]: the rows of box d that fit under the clamp, 0 for a dropped box.
+ * sub_off (D+1) int64 = the exclusive prefix sum of (cnt_stored[d] > cap ? cap : 0): box d's slice of the subsample table, empty
+ * for a box of at most `cap` stored rows.  Every output is written on every call; the limits are fcn_frustum_train_plan_limits'.
+ * NULL pointers, D < 0, S < 1, cap < 1, capacity < 0: FCN_E_BADARG; D > 2048 or D * S > 65536: FCN_E_LIMIT; nothing written. */
+int fcn_frustum_sunrgbd_train_plan(const int32_t *seg_cnt, const int32_t *seg_pos, int min_positives, int cap, int D, int S,
+                                   int64_t capacity, int64_t *seg_off, int64_t *row0, int32_t *cnt_stored, int64_t *sub_off,
+                                   int32_t *status, void *stream);
+/* fcn_frustum_subsample_draw: the reference's rng.choice(n, cap, replace=False) of every frustum over `cap` rows
+ * (sunrgbd/prepare_data.py:219-224), on the draws' stream.  For every box d with sub_off[d + 1] > sub_off[d]:
+ * sub[sub_off[d] + i], i < cap, = row d of fcn_draw_batch's choice at N = cap, n = cnt_stored[d] (tag 0: the indices of the `cap`
+ * smallest composites, ascending by composite) -- the same kernel, so `cap` distinct indices in [0, cnt_stored[d]).  Nothing else of
+ * sub is written.  A box with such a slice and cnt_stored[d] <= 0 gets zeros and bit 0 of *status (the plan never produces one).
+ * D == 0: the pass-through.  advance != 0: state[0] + 1 is left behind.  NULL pointers, D < 0, cap < 1: FCN_E_BADARG; cap > the
+ * largest N of fcn_draw_limits: FCN_E_LIMIT; nothing written. */
+int fcn_frustum_subsample_draw(const int32_t *cnt_stored, const int64_t *sub_off, int D, int cap, uint64_t seed, int64_t *state,
+                               int advance, int32_t *sub, int32_t *status, void *stream);
+/* fcn_frustum_sunrgbd_train_slots: behind fcn_frustum_subset_pos (U = D, off = row0, cnt = cnt_stored -> pos (D) int32).  Box d
+ * survives iff it is pre-kept (seg_pos, as in the plan) and pos[d] >= min_positives.  The first B survivors in box order take slots
+ * 0..n-1; for slot i < n with box d: slot_box[i] = d, off[i] = row0[d], counts[i] = cnt_stored[d], sub_start[i] = sub_off[d] and
+ * sub_len[i] = sub_off[d + 1] - sub_off[d] (both 0 for a box without a subsample).  For an empty slot i >= n: slot_box 0, off =
+ * capacity (the spare row of the point buffer), counts 0, sub_start 0, sub_len 0.  *n_kept = n; n < B sets bit 1.  slot_box (B) int32,
+ * off, counts, sub_start (B) int64, sub_len (B) int32.  Every output is written on every call.
+ * NULL pointers, D < 0, S < 1, B < 1, capacity < 0: FCN_E_BADARG; D or B > 2048 or D * S > 65536: FCN_E_LIMIT; nothing written. */
+int fcn_frustum_sunrgbd_train_slots(const int32_t *seg_pos, const int32_t *pos, const int64_t *row0, const int32_t *cnt_stored,
+                                    const int64_t *sub_off, int min_positives, int D, int S, int B, int64_t capacity,
+                                    int32_t *slot_box, int32_t *n_kept, int64_t *off, int64_t *counts, int64_t *sub_start,
+                                    int32_t *sub_len, int32_t *status, void *stream);
+/* fcn_draw_batch with the subsample slices given per row: where sub_len[b] > 0, row b's n is sub_len[b] and the value written is
+ * sub[sub_start[b] + c] instead of c (sub_start, sub_len: B entries each, the slices need not be packed or ordered).  The same
+ * words, tags, scalars and status bit; given slices that happen to be packed it equals fcn_draw_batch bit for bit.  sub, sub_start
+ * and sub_len are required; otherwise the refusals of fcn_draw_batch. */
+int fcn_draw_batch_sliced(const fcn_draw_desc *d, const int64_t *counts, const int32_t *sub, const int64_t *sub_start,
+                          const int32_t *sub_len, uint64_t seed, int64_t *state, int32_t *choice, double *coin, double *normal,
+                          double *hshift, int32_t *status, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
  * The cascade link for TRAINING the refinement stage: first-stage detections + the frames' label boxes -> the labelled raw
  * records fcn_prepare_inputs_refine takes.  Replaces the host loop of kitti/prepare_data_refine.py::extract_frustum_det_data
  * (:406-592) and, with the label boxes themselves as detections, of extract_frustum_data (:239-403).

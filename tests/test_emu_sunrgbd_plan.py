@@ -1,0 +1,48 @@
+"""The -m gpu tests of the capturable SUN-RGBD training input (tests/test_gpu_sunrgbd_plan.py), run on the CPU: the SAME test
+functions with the package's GPU-only Python layer pointed at the host emulation of the kernels (tests/emu_shim.py +
+tests/host_harness).  The emulated library exports the new entries like every other entry point (csrc/frustum_sunrgbd_plan.h is
+included from inputs.hip).  Left out: the test that needs a real graph capture.  The hardware run stays the gate; this tier catches
+index, order and bounds mistakes in the kernels and in SunrgbdTrainSource without a GPU."""
+import os
+import shutil
+
+import pytest
+
+CLANG = os.environ.get("FCN_HOST_CLANG", "/opt/rocm/lib/llvm/bin/clang++")
+pytestmark = pytest.mark.skipif(not (os.path.exists(CLANG) or shutil.which(CLANG)), reason="host clang++ not available")
+
+CASES = [
+    ("test_perturb_equals_the_restatement_bit_for_bit", (1, 0)),
+    ("test_perturb_equals_the_restatement_bit_for_bit", (1, 1)),
+    ("test_perturb_equals_the_restatement_bit_for_bit", (1, 2 ** 32 + 5)),
+    ("test_perturb_equals_the_restatement_bit_for_bit", (300, 0)),
+    ("test_perturb_equals_the_restatement_bit_for_bit", (300, 1)),
+    ("test_perturb_equals_the_restatement_bit_for_bit", (300, 2 ** 32 + 5)),
+    ("test_no_read_count_and_fill_equal_the_label_entries_bit_for_bit", (3,)),
+    ("test_no_read_count_and_fill_equal_the_label_entries_bit_for_bit", (6,)),
+    ("test_plan_subsample_and_slots_equal_the_restatement", (4,)),
+    ("test_plan_subsample_and_slots_equal_the_restatement", (12,)),
+    ("test_plan_subsample_and_slots_at_their_smallest_and_over_many_boxes", ()),
+    ("test_subsample_of_more_rows_than_the_draws_sort_whole", ()),
+    ("test_sliced_draw_equals_the_packed_draw_and_reads_the_right_slice", ()),
+    ("test_step_equals_the_existing_path_on_the_same_boxes", (12, 3, None, True)),
+    ("test_step_equals_the_existing_path_on_the_same_boxes", (12, 6, None, True)),
+    ("test_step_equals_the_existing_path_on_the_same_boxes", (4, 6, (0, 1, 2, 3), True)),
+    ("test_step_equals_the_existing_path_on_the_same_boxes", (4, 3, (10, 0, 9, 1), False)),
+    ("test_exact_cells_are_subsampled_on_either_side_of_cap", ()),
+    ("test_large_cap_takes_the_radix_select_inside_a_step", ()),
+    ("test_overflow_is_truncated_flagged_and_stays_in_bounds", ()),
+    ("test_step_reproduces_the_references_recorded_run", ()),
+    ("test_one_training_step_on_a_step_batch", ()),
+    ("test_constructor_refusals", ()),
+    ("test_entry_refusals_write_nothing", ()),
+    ("test_check_raises_names_the_bits_and_clears", ()),
+]
+
+
+@pytest.mark.parametrize("fn,args", CASES, ids=["%s-%s" % (c[0][5:45], "_".join(str(a) for a in c[1])) for c in CASES])
+def test_sunrgbd_plan_under_emulation(fn, args):
+    import test_gpu_sunrgbd_plan as m
+    from emu_shim import emulated_gpu
+    with emulated_gpu():
+        getattr(m, fn)(*(list(a) if isinstance(a, tuple) else a for a in args))
