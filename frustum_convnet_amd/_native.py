@@ -96,7 +96,9 @@ EXPORTS = ("fcn_arch", "fcn_build_hash", "fcn_stat_replicas", "fcn_query_depth_p
            "fcn_box2d_perturb", "fcn_box2d_perturb_limits", "fcn_frustum_train_count", "fcn_frustum_train_fill", "fcn_frustum_train_plan",
            "fcn_frustum_train_plan_limits",
            "fcn_box2d_perturb_sunrgbd", "fcn_frustum_sunrgbd_train_count", "fcn_frustum_sunrgbd_train_fill",
-           "fcn_frustum_sunrgbd_train_plan", "fcn_frustum_subsample_draw", "fcn_frustum_sunrgbd_train_slots", "fcn_draw_batch_sliced")
+           "fcn_frustum_sunrgbd_train_plan", "fcn_frustum_subsample_draw", "fcn_frustum_sunrgbd_train_slots", "fcn_draw_batch_sliced",
+           "fcn_refine_train_match", "fcn_refine_train_count", "fcn_refine_train_fill", "fcn_box3d_jitter_draw", "fcn_refine_train_plan",
+           "fcn_refine_train_plan_limits")
 
 _lib = None
 
@@ -317,6 +319,20 @@ def lib():
         L.fcn_frustum_sunrgbd_train_slots.argtypes = [c_fp] * 5 + [ctypes.c_int] * 4 + [ctypes.c_int64] + [c_fp] * 8
         L.fcn_draw_batch_sliced.restype = ctypes.c_int
         L.fcn_draw_batch_sliced.argtypes = [ctypes.POINTER(DrawDesc)] + [c_fp] * 4 + [ctypes.c_uint64] + [c_fp] * 7
+    if hasattr(L, "fcn_refine_train_plan") or "FCN_LIB_NAME" not in os.environ:
+        L.fcn_refine_train_match.restype = ctypes.c_int
+        L.fcn_refine_train_match.argtypes = L.fcn_refine_match.argtypes
+        L.fcn_refine_train_count.restype = ctypes.c_int
+        L.fcn_refine_train_count.argtypes = rl_in + [c_fp] * 9
+        L.fcn_refine_train_fill.restype = ctypes.c_int
+        L.fcn_refine_train_fill.argtypes = rl_in + [c_fp] * 3
+        L.fcn_box3d_jitter_draw.restype = ctypes.c_int
+        L.fcn_box3d_jitter_draw.argtypes = [ctypes.c_int] * 2 + [ctypes.c_uint64, c_fp, ctypes.c_int, c_fp, c_fp]
+        L.fcn_refine_train_plan.restype = ctypes.c_int
+        L.fcn_refine_train_plan.argtypes = ([c_fp] * 3 + [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int32)] +
+                                            [ctypes.c_int] * 3 + [ctypes.c_int64] + [c_fp] * 7)
+        L.fcn_refine_train_plan_limits.restype = ctypes.c_int
+        L.fcn_refine_train_plan_limits.argtypes = [ctypes.POINTER(ctypes.c_int)] * 2
     L.fcn_rotate_nms_3d.restype = ctypes.c_int
     L.fcn_rotate_nms_3d.argtypes = [c_fp] * 3 + [ctypes.c_int] * 3 + [ctypes.c_float, ctypes.c_int] + [c_fp] * 3
     _lib = L

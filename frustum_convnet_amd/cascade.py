@@ -11,8 +11,12 @@ fallback.
 
 Training the refinement stage on the first stage's output (extract_frustum_det_data :406-592: match to the labels, enlarge, jitter,
 select, count the positives, reject) is match_detections + draw_box3d_jitter + refine_training_candidates (C-ABI fcn_refine_match,
-fcn_refine_label_count / _fill, csrc/refine_label.h) and RefineInputBuilder.build_device_train.
+fcn_refine_label_count / _fill, csrc/refine_label.h) and RefineInputBuilder.build_device_train.  RefineTrainSource is the same link
+as ONE capturable sequence of launches at a fixed batch size and fixed window counts, with no host read (C-ABI
+fcn_refine_train_match / _count / _plan / _fill, fcn_box3d_jitter_draw, csrc/refine_plan.h).
 """
+import ctypes
+
 import numpy as np
 import torch
 
@@ -188,6 +192,229 @@ def refine_training_candidates(frame_points, frame_off, dets, cand_row, cand_fra
             "box3d": pick(gc), "heading": pick(gh), "size": pick(gs), "cnt": pick(both[0].sum(1, dtype=torch.int32)),
             "pos": pick(both[1].sum(1, dtype=torch.int32)), "kept": kept, "unit_cand": kept // A,
             "counts": seg_counts.sum(1)[kept]}
+
+
+# ------------------------------------------------------------------------------------------------
+# The refinement stage's training input as ONE capturable sequence of launches (csrc/refine_plan.h)
+STATUS_BITS = ((1, "bit 0: a slot had no row to draw from (its choice row is zeros)"),
+               (2, "bit 1: fewer units survived than the batch has slots (the empty slots hold the spare unit box over no rows)"),
+               (4, "bit 2: the selected rows exceed the capacity of the point buffer (the overflow was dropped)"),
+               (32, "bit 5: a unit's predicted width needs more windows than lpad on some stride (the unit was dropped)"),
+               (64, "bit 6: a unit's predicted width is not a positive finite number (the unit was dropped)"))
+
+
+class RefineTrainSource:
+    """Resident frames, a resident table of first-stage detections and the label boxes -> the RefineInputBuilder training batch at
+    a FIXED batch size B and FIXED window counts lpad, every step, with no host read and no upload: what match_detections +
+    draw_box3d_jitter + refine_training_candidates + RefineInputBuilder.build_device_train(draws=DeviceDraws) do behind their
+    synchronisations, as one sequence of launches that can be captured into a hipGraph and draws anew on every replay
+    (INTEGRATION.md "Capturable refine-stage training input" states the contract).
+    frame_points / frame_off as refine_candidates takes them; dets (R,8) float32 ON THE DEVICE, contiguous: HELD, not copied -- a
+    caller may overwrite it in place between steps with the first stage's fresh output; det_frame (R) the frame and det_types (R
+    names) the class of each row; gt_box3d (G,7) / gt_off (F+1) as match_detections takes them; builder: a RefineInputBuilder;
+    B: slots of the batch; D: detections tried per step; A: chained jittered copies per detection (units u = d * A + a; B <= D * A,
+    D <= R, D * A <= 2048); capacity: rows of the point buffer (rows beyond it are dropped and flagged); lpad: four ints, the
+    padded window counts of center_ref1..4 (a unit whose predicted width needs more is dropped and flagged); seed: the three
+    generators are DeviceDraws keyed seed (detection pick), seed + 1 (box jitter), seed + 2 (per-sample draws), each one step
+    further after every step().  pick=False: the first D detections in order; jitter=False: A = 1 without jitter; jitter=<(D,A,7)
+    array>: that fixed table of uniforms on every step.
+    Everything is validated here, once, on the host; step() validates nothing and reads nothing."""
+
+    def __init__(self, frame_points, frame_off, dets, det_frame, det_types, gt_box3d, gt_off, builder, B, D, A, capacity, lpad,
+                 seed, thresh=0.5, ratio=1.2, shift_ratio=0.05, pick=True, jitter=True):
+        from .inputs import DeviceDraws
+        who = "RefineTrainSource"
+        _need_cuda(frame_points, who)
+        dev = frame_points.device
+        L = _native.lib()
+        pts = frame_points.detach().contiguous().float()
+        if pts.dim() != 2 or pts.shape[1] < 3:
+            raise ValueError("%s: frame_points must be (n, >= 3), got %s" % (who, tuple(frame_points.shape)))
+        foff_h = torch.as_tensor(frame_off).detach().cpu().to(torch.int64).contiguous().view(-1).numpy()
+        F, ps = len(foff_h) - 1, int(pts.shape[1])
+        if F < 1 or foff_h[0] < 0 or (np.diff(foff_h) < 0).any() or foff_h[-1] > pts.shape[0]:
+            raise ValueError("%s: frame_off must be F + 1 >= 2 ascending row offsets into the %d rows" % (who, pts.shape[0]))
+        seg = int(L.fcn_frustum_select_seg())
+        S = max(1, -(-int(np.diff(foff_h).max()) // seg))       # no frame is longer than S segments: checked HERE, once
+        if pts.shape[0] == 0:
+            pts = torch.zeros((1, ps), dtype=torch.float32, device=dev)
+        if not (isinstance(dets, torch.Tensor) and dets.is_cuda and dets.dtype == torch.float32 and dets.is_contiguous()
+                and dets.dim() == 2 and dets.shape[1] == 8 and not dets.requires_grad):
+            raise ValueError("%s: dets must be a contiguous (R, 8) float32 device tensor (it is held, not copied)" % who)
+        R = int(dets.shape[0])
+        host = lambda a: (a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a))
+        dfr = np.ascontiguousarray(host(det_frame)).reshape(-1)
+        types = [str(t) for t in det_types]
+        if len(dfr) != R or len(types) != R:
+            raise ValueError("%s: %d dets, %d det_frame, %d det_types" % (who, R, len(dfr), len(types)))
+        if R == 0 or dfr.dtype.kind not in "iu" or int(dfr.min()) < 0 or int(dfr.max()) >= F:
+            raise ValueError("%s: det_frame must hold integers in [0, %d)" % (who, F))
+        gt = np.ascontiguousarray(host(gt_box3d), dtype=np.float64).reshape(-1, 7)
+        goff_h = np.ascontiguousarray(host(gt_off)).reshape(-1).astype(np.int64)
+        G = len(gt)
+        if len(goff_h) != F + 1 or goff_h[0] < 0 or (np.diff(goff_h) < 0).any() or goff_h[-1] > G:
+            raise ValueError("%s: gt_off must be %d ascending row offsets into the %d label boxes" % (who, F + 1, G))
+        if G == 0:
+            raise ValueError("%s: no label box" % who)
+        fixed = None
+        if isinstance(jitter, (bool, np.bool_)):
+            if not jitter and int(A) != 1:
+                raise ValueError("%s: jitter=False goes with A = 1, got A = %d" % (who, int(A)))
+        else:
+            fixed = np.ascontiguousarray(host(jitter), dtype=np.float64)
+            if fixed.shape != (int(D), int(A), 7):
+                raise ValueError("%s: a jitter table must be (D, A, 7) = (%d, %d, 7), got %s" % (who, int(D), int(A), fixed.shape))
+        B, D, A, capacity = int(B), int(D), int(A), int(capacity)
+        a, b = ctypes.c_int(0), ctypes.c_int(0)
+        _native.check(L.fcn_refine_train_plan_limits(ctypes.byref(a), ctypes.byref(b)), "fcn_refine_train_plan_limits")
+        max_u, max_segs = a.value, b.value
+        if not (1 <= A <= 64):
+            raise ValueError("%s: A must lie in [1, 64], got %d" % (who, A))
+        U = D * A
+        if not (1 <= B <= U and 1 <= D <= R) or U > max_u:
+            raise ValueError("%s: need 1 <= B <= D * A, D <= R and D * A <= %d, got B = %d, D = %d, A = %d, R = %d" %
+                             (who, max_u, B, D, A, R))
+        if U * S > max_segs:
+            raise ValueError("%s: D * A * S = %d * %d segments exceed the plan's %d" % (who, U, S, max_segs))
+        if capacity < 1:
+            raise ValueError("%s: capacity must be >= 1 row, got %d" % (who, capacity))
+        lpad = [int(x) for x in lpad]
+        if len(lpad) != 4 or min(lpad) < 1:
+            raise ValueError("%s: lpad must be four window counts >= 1, got %r" % (who, lpad))
+        r = float(shift_ratio)
+        if not (0.0 <= r < 1.0) or not (float(ratio) > 0.0):
+            raise ValueError("%s: shift_ratio must lie in [0, 1) and ratio be positive, got %r, %r" % (who, shift_ratio, ratio))
+        if builder.device.type != "cuda":
+            raise RuntimeError("frustum_convnet_amd: input construction is a HIP kernel (MI355X only); no CPU fallback")
+        cls = [builder.classes.index(t) if t in builder.classes else -1 for t in types]
+        if min(cls) < 0:
+            raise ValueError("%s: type %r is not one of %r" % (who, types[cls.index(-1)], tuple(builder.classes)))
+        self.device, self.builder, self.lpad = dev, builder, lpad
+        self.B, self.D, self.A, self.U, self.R, self.G, self.F, self.S, self.ps, self.capacity = B, D, A, U, R, G, F, S, ps, capacity
+        self.pick, self.draw_jitter = bool(pick), fixed is None and bool(jitter)
+        self.thresh, self.ratio, self.shift_ratio = float(thresh), float(ratio), r
+        up = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(dev)
+        f64, i32, i64 = (dict(dtype=t, device=dev) for t in (torch.float64, torch.int32, torch.int64))
+        N = builder.npoints
+        # ---- resident: the frames, the detections (held), the labels
+        self.frames = (pts, up(foff_h))
+        self.dets = dets
+        self.det_frame, self.det_class = up(dfr.astype(np.int32)), up(np.asarray(cls, dtype=np.int64).reshape(R, 1))
+        self.gt, self.gt_off = up(gt), up(goff_h)
+        self.eye = torch.eye(len(builder.classes), dtype=torch.float32, device=dev)
+        self.r_count = torch.full((1,), R, **i64)
+        self.strides_c = (ctypes.c_double * 4)(*builder.strides)
+        self.lpad_c = (ctypes.c_int32 * 4)(*lpad)
+        # ---- the generators
+        seed = int(seed)
+        self.draws_pick, self.draws_jitter, self.draws_sample = (DeviceDraws(seed + k, builder.device) for k in range(3))
+        self.status = torch.zeros((1,), **i32)
+        # ---- every intermediate
+        self.cand_row = torch.arange(D, **i32).view(1, D)
+        self.pick_scalars = (torch.zeros((1,), **f64), torch.zeros((1,), **f64))
+        self.cand_frame = torch.zeros((D,), **i32)
+        self.cand_class = torch.zeros((D + 1, 1), **i64)        # row D: the spare entry's class, 0
+        self.gt_idx, self.best_iou = torch.full((D,), -1, **i32), torch.zeros((D,), dtype=torch.float32, device=dev)
+        self.jitter = None if (fixed is None and not jitter) else (torch.zeros((D, A, 7), **f64) if fixed is None else up(fixed))
+        self.both = torch.zeros((2, U, S), **i32)               # selected, positive
+        # the per-unit tables have U + 1 rows: row U is the spare entry an empty slot gathers -- a unit box at the origin, its
+        # label box equal to the predicted one -- written here once and never by a kernel
+        hx, hz = np.asarray([1, 1, -1, -1, 1, 1, -1, -1]) * 0.5, np.asarray([1, -1, -1, 1, 1, -1, -1, 1]) * 0.5
+        hy = np.asarray([1, 1, 1, 1, -1, -1, -1, -1]) * 0.5
+        spare = torch.from_numpy(np.stack([hx, hy, hz], 1).reshape(24)).to(dev)
+        self.pred_box3d, self.box3d = torch.zeros((U + 1, 24), **f64), torch.zeros((U + 1, 24), **f64)
+        self.pred_angle, self.heading = torch.zeros((U + 1,), **f64), torch.zeros((U + 1,), **f64)
+        self.pred_size, self.size = torch.zeros((U + 1, 3), **f64), torch.zeros((U + 1, 3), **f64)
+        for tab in (self.pred_box3d, self.box3d):
+            tab[U] = spare
+        for tab in (self.pred_size, self.size):
+            tab[U] = 1.0
+        self.slot_unit, self.slot_cand, self.n_kept = torch.full((B,), U, **i32), torch.full((B,), D, **i32), torch.zeros((1,), **i32)
+        self.unit_cand = torch.div(torch.arange(U + 1, **i32), A, rounding_mode="floor").to(torch.int32)     # row U -> D
+        self.seg_off, self.off = torch.zeros((U * S + 1,), **i64), torch.zeros((B + 1,), **i64)
+        self.counts = torch.zeros((B,), **i64)
+        # the spare row is what an empty slot's all-zero choice row reads: fcn_prepare_inputs_refine indexes off[b] + choice
+        self.points = torch.zeros((capacity + 1, ps), dtype=torch.float32, device=dev)
+        self.t = {"raw": self.points, "off": self.off, "choice": torch.zeros((B, N), **i32),
+                  "pcorners": torch.zeros((B, 24), **f64), "pangle": torch.zeros((B,), **f64), "psize": torch.zeros((B, 3), **f64),
+                  "corners": torch.zeros((B, 24), **f64), "heading": torch.zeros((B,), **f64), "size": torch.zeros((B, 3), **f64),
+                  "coin": torch.zeros((B,), **f64), "normal": torch.zeros((B,), **f64)}
+        self.out = builder.alloc(B, lpad, True)
+        self.out["size_class"] = torch.zeros((B, 1), **i64)
+        if builder.one_hot:
+            self.out["one_hot"] = torch.zeros((B, len(builder.classes)), dtype=torch.float32, device=dev)
+        if not self.pick:                                       # the first D detections, gathered once
+            self._gather_candidates()
+
+    @staticmethod
+    def limits():
+        """(the largest D * A, the largest D * A * S) of the plan."""
+        a, b = ctypes.c_int(0), ctypes.c_int(0)
+        _native.check(_native.lib().fcn_refine_train_plan_limits(ctypes.byref(a), ctypes.byref(b)), "fcn_refine_train_plan_limits")
+        return a.value, b.value
+
+    def _gather_candidates(self):
+        idx = self.cand_row.view(-1)
+        torch.index_select(self.det_frame, 0, idx, out=self.cand_frame)
+        torch.index_select(self.det_class, 0, idx, out=self.cand_class[:self.D])
+
+    def step(self):
+        """Enqueues one batch on the current stream -- pick, gather, match, jitter draw, count, plan, fill, gather, draw,
+        fcn_prepare_inputs_refine -- and nothing else: no allocation, no host read, no upload (capturable).  Returns the batch dict
+        of RefineInputBuilder.build(), same keys and dtypes, at batch size B and window counts lpad; the same tensors every step.
+        Kept for inspection: cand_row (1,D) the detections tried, gt_idx / best_iou (D) their match, jitter (D,A,7) the step's
+        uniforms, pred_box3d / pred_angle / pred_size (U+1 rows) the jittered enlarged boxes, slot_unit (B) the unit of each slot
+        (U: empty), n_kept (1) the filled slots; check() reads the status words."""
+        L, dev, bld = _native.lib(), self.device, self.builder
+        B, D, A, U, S, t = self.B, self.D, self.A, self.U, self.S, self.t
+        p = lambda x: None if x is None else x.data_ptr()
+        pts, foff = self.frames
+        with torch.cuda.device(dev):
+            s = _native.current_stream(dev)
+            if self.pick:
+                self.draws_pick.draw(self.r_count, D, False, False, out=(self.cand_row,) + self.pick_scalars)
+                self._gather_candidates()
+            else:                                               # (the three step counters stay equal)
+                _native.check(L.fcn_box3d_jitter_draw(0, 1, self.draws_pick.seed, p(self.draws_pick.state), 1, p(self.pick_scalars[0]), s),
+                              "fcn_box3d_jitter_draw")
+            crow = self.cand_row.view(-1)
+            _native.check(L.fcn_refine_train_match(p(self.dets), self.R, p(crow), p(self.cand_frame), D, p(self.gt), self.G,
+                                                   p(self.gt_off), self.F, self.thresh, p(self.gt_idx), p(self.best_iou), s),
+                          "fcn_refine_train_match")
+            _native.check(L.fcn_box3d_jitter_draw(D if self.draw_jitter else 0, A, self.draws_jitter.seed, p(self.draws_jitter.state), 1,
+                                                  p(self.jitter if self.draw_jitter else self.pick_scalars[0]), s),
+                          "fcn_box3d_jitter_draw")
+            args = (p(pts), p(foff), self.F, self.ps, p(self.dets), self.R, p(crow), p(self.cand_frame), D, self.ratio, p(self.gt_idx),
+                    p(self.gt), self.G, A, p(self.jitter), self.shift_ratio, S)
+            _native.check(L.fcn_refine_train_count(*args, p(self.both[0]), p(self.both[1]), p(self.pred_box3d), p(self.pred_angle),
+                                                   p(self.pred_size), p(self.box3d), p(self.heading), p(self.size), s),
+                          "fcn_refine_train_count")
+            _native.check(L.fcn_refine_train_plan(p(self.both[0]), p(self.both[1]), p(self.pred_size), self.strides_c, self.lpad_c, U, S,
+                                                  B, self.capacity, p(self.slot_unit), p(self.n_kept), p(self.seg_off), p(self.off),
+                                                  p(self.counts), p(self.status), s), "fcn_refine_train_plan")
+            _native.check(L.fcn_refine_train_fill(*args, p(self.seg_off), p(self.points), s), "fcn_refine_train_fill")
+            for src, dst in ((self.pred_box3d, t["pcorners"]), (self.pred_angle, t["pangle"]), (self.pred_size, t["psize"]),
+                             (self.box3d, t["corners"]), (self.heading, t["heading"]), (self.size, t["size"])):
+                torch.index_select(src, 0, self.slot_unit, out=dst)
+            torch.index_select(self.unit_cand, 0, self.slot_unit, out=self.slot_cand)
+            torch.index_select(self.cand_class, 0, self.slot_cand, out=self.out["size_class"])
+            if "one_hot" in self.out:
+                torch.index_select(self.eye, 0, self.out["size_class"].view(-1), out=self.out["one_hot"])
+            self.draws_sample.draw(self.counts, bld.npoints, bld.random_flip, bld.random_shift,
+                                   out=(t["choice"], t["coin"], t["normal"]))
+            return bld.launch(t, self.out, self.ps, self.lpad, True)
+
+    def check(self):
+        """Reads the status words of the plan and the three generators (a synchronisation: not for a captured region); raises
+        ValueError naming the bits set since the last check() and clears them."""
+        words = (self.status, self.draws_pick.status, self.draws_jitter.status, self.draws_sample.status)
+        s = 0
+        for v in torch.cat(words).cpu().tolist():
+            s |= int(v)
+        if s:
+            for w in words:
+                w.zero_()
+            raise ValueError("RefineTrainSource: status %d -- %s" % (s, "; ".join(text for bit, text in STATUS_BITS if s & bit)))
 
 
 class TwoStageDetector:

@@ -486,3 +486,9 @@ extern "C" int fcn_prepare_inputs_refine(const fcn_inp_refine_desc *d, const flo
 // slices (fcn_box2d_perturb_sunrgbd, fcn_frustum_sunrgbd_train_count / _plan / _fill / _slots, fcn_frustum_subsample_draw,
 // fcn_draw_batch_sliced): csrc/frustum_sunrgbd_plan.h
 #include "frustum_sunrgbd_plan.h"
+
+// ------------------------------------------------------------------------------------------------
+// The refinement stage's training input without a host read: the match and the labelled count / fill without their read-backs, the
+// box jitter drawn on the device and the one-workgroup plan between count and fill (fcn_refine_train_match / _count / _fill,
+// fcn_box3d_jitter_draw, fcn_refine_train_plan): csrc/refine_plan.h
+#include "refine_plan.h"

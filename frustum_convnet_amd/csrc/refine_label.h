@@ -246,9 +246,14 @@ __global__ __launch_bounds__(RL_MT) void rl_match_kernel(RlMatchArgs a)
     }
 }
 
-extern "C" int fcn_refine_match(const float *dets, int R, const int32_t *cand_row, const int32_t *cand_frame, int D,
-                                const double *gt_box3d, int G, const int64_t *gt_off, int F, double thresh, int32_t *gt_idx,
-                                float *best_iou, void *stream)
+// What the entries below and the no-read entries of refine_plan.h (fcn_refine_train_match / _count / _fill) share: the argument
+// checks, the kernels' arguments and the launch.  read_lists: read the index lists back first (rs_candidates_in_range, rl_read_lists:
+// a synchronisation) and report a candidate out of range or a frame longer than S segments; without it nothing is read and 0 is
+// returned once the launch is enqueued -- the kernels skip a candidate whose row, frame or label is out of range either way, the
+// length condition is the caller's then.
+static inline int rl_match_launch(const float *dets, int R, const int32_t *cand_row, const int32_t *cand_frame, int D,
+                                  const double *gt_box3d, int G, const int64_t *gt_off, int F, double thresh, int32_t *gt_idx,
+                                  float *best_iou, void *stream, bool read_lists)
 {
     if (D < 0 || F < 0 || R < 0 || G < 0) return FCN_E_BADARG;
     if (D == 0) return 0;
@@ -259,14 +264,24 @@ extern "C" int fcn_refine_match(const float *dets, int R, const int32_t *cand_ro
         return (int)e;
     }
     if (!dets || !cand_row || !cand_frame || !gt_off || (G > 0 && !gt_box3d)) return FCN_E_BADARG;
-    bool ok = false;
-    FCN_TRY(rs_candidates_in_range(cand_row, cand_frame, D, R, F, (hipStream_t)stream, &ok));
+    bool ok = true;
+    if (read_lists) {
+        ok = false;
+        FCN_TRY(rs_candidates_in_range(cand_row, cand_frame, D, R, F, (hipStream_t)stream, &ok));
+    }
     RlMatchArgs a;
     a.dets = dets; a.crow = cand_row; a.cframe = cand_frame; a.gt = gt_box3d; a.goff = gt_off;
     a.R = R; a.D = D; a.G = G; a.F = F; a.thresh = thresh; a.gidx = gt_idx; a.best = best_iou;
     hipLaunchKernelGGL(rl_match_kernel, dim3((D + RL_MT / 64 - 1) / (RL_MT / 64)), dim3(RL_MT), 0, (hipStream_t)stream, a);
     FCN_CHECK_LAUNCH();
     return ok ? 0 : FCN_E_BADARG;
+}
+
+extern "C" int fcn_refine_match(const float *dets, int R, const int32_t *cand_row, const int32_t *cand_frame, int D,
+                                const double *gt_box3d, int G, const int64_t *gt_off, int F, double thresh, int32_t *gt_idx,
+                                float *best_iou, void *stream)
+{
+    return rl_match_launch(dets, R, cand_row, cand_frame, D, gt_box3d, G, gt_off, F, thresh, gt_idx, best_iou, stream, true);
 }
 
 // ---- count / fill
@@ -301,12 +316,12 @@ static inline bool rl_sizes_ok(int F, int pt_stride, int R, int D, int G, int A,
     return (int64_t)D * A <= FS_MAX_D;         // units are the grid's y dimension
 }
 
-extern "C" int fcn_refine_label_count(const float *frame_pts, const int64_t *frame_off, int F, int pt_stride, const float *dets,
-                                      int R, const int32_t *cand_row, const int32_t *cand_frame, int D, double ratio,
-                                      const int32_t *cand_gt, const double *gt_box3d, int G, int A, const double *jitter,
-                                      double shift_ratio, int S, int32_t *seg_cnt, int32_t *seg_pos, double *pred_corners,
-                                      double *pred_angle, double *pred_size, double *gt_corners, double *gt_heading,
-                                      double *gt_size, void *stream)
+static inline int rl_count_launch(const float *frame_pts, const int64_t *frame_off, int F, int pt_stride, const float *dets,
+                                  int R, const int32_t *cand_row, const int32_t *cand_frame, int D, double ratio,
+                                  const int32_t *cand_gt, const double *gt_box3d, int G, int A, const double *jitter,
+                                  double shift_ratio, int S, int32_t *seg_cnt, int32_t *seg_pos, double *pred_corners,
+                                  double *pred_angle, double *pred_size, double *gt_corners, double *gt_heading,
+                                  double *gt_size, void *stream, bool read_lists)
 {
     if (!rl_sizes_ok(F, pt_stride, R, D, G, A, S)) return FCN_E_BADARG;
     if (D == 0) return 0;
@@ -320,9 +335,12 @@ extern "C" int fcn_refine_label_count(const float *frame_pts, const int64_t *fra
     if (!frame_pts || !frame_off || !dets || !cand_row || !cand_frame || !cand_gt || !gt_box3d || !pred_corners || !pred_angle ||
         !pred_size || !gt_corners || !gt_heading || !gt_size)
         return FCN_E_BADARG;
-    bool ok = false, ok_gt = false, fits = false;
-    FCN_TRY(rs_candidates_in_range(cand_row, cand_frame, D, R, F, (hipStream_t)stream, &ok));
-    FCN_TRY(rl_read_lists(cand_gt, frame_off, D, G, F, S, (hipStream_t)stream, &ok_gt, &fits));
+    bool ok = true, ok_gt = true, fits = true;
+    if (read_lists) {
+        ok = false; ok_gt = false; fits = false;
+        FCN_TRY(rs_candidates_in_range(cand_row, cand_frame, D, R, F, (hipStream_t)stream, &ok));
+        FCN_TRY(rl_read_lists(cand_gt, frame_off, D, G, F, S, (hipStream_t)stream, &ok_gt, &fits));
+    }
     if (!fits) return FCN_E_BADARG;
     RlArgs a;
     a.r.pts = frame_pts; a.r.foff = frame_off; a.r.dets = dets; a.r.crow = cand_row; a.r.cframe = cand_frame; a.r.ooff = nullptr;
@@ -339,10 +357,10 @@ extern "C" int fcn_refine_label_count(const float *frame_pts, const int64_t *fra
     return (ok && ok_gt) ? 0 : FCN_E_BADARG;
 }
 
-extern "C" int fcn_refine_label_fill(const float *frame_pts, const int64_t *frame_off, int F, int pt_stride, const float *dets,
-                                     int R, const int32_t *cand_row, const int32_t *cand_frame, int D, double ratio,
-                                     const int32_t *cand_gt, const double *gt_box3d, int G, int A, const double *jitter,
-                                     double shift_ratio, int S, const int64_t *seg_off, float *out_pts, void *stream)
+static inline int rl_fill_launch(const float *frame_pts, const int64_t *frame_off, int F, int pt_stride, const float *dets,
+                                 int R, const int32_t *cand_row, const int32_t *cand_frame, int D, double ratio,
+                                 const int32_t *cand_gt, const double *gt_box3d, int G, int A, const double *jitter,
+                                 double shift_ratio, int S, const int64_t *seg_off, float *out_pts, void *stream, bool read_lists)
 {
     if (!rl_sizes_ok(F, pt_stride, R, D, G, A, S)) return FCN_E_BADARG;
     if (D == 0) return 0;
@@ -350,9 +368,12 @@ extern "C" int fcn_refine_label_fill(const float *frame_pts, const int64_t *fram
     if (F == 0) return 0;
     if (!frame_pts || !frame_off || !dets || !cand_row || !cand_frame || !cand_gt || !gt_box3d || !seg_off || !out_pts)
         return FCN_E_BADARG;
-    bool ok = false, ok_gt = false, fits = false;
-    FCN_TRY(rs_candidates_in_range(cand_row, cand_frame, D, R, F, (hipStream_t)stream, &ok));
-    FCN_TRY(rl_read_lists(cand_gt, frame_off, D, G, F, S, (hipStream_t)stream, &ok_gt, &fits));
+    bool ok = true, ok_gt = true, fits = true;
+    if (read_lists) {
+        ok = false; ok_gt = false; fits = false;
+        FCN_TRY(rs_candidates_in_range(cand_row, cand_frame, D, R, F, (hipStream_t)stream, &ok));
+        FCN_TRY(rl_read_lists(cand_gt, frame_off, D, G, F, S, (hipStream_t)stream, &ok_gt, &fits));
+    }
     if (!fits) return FCN_E_BADARG;
     RlArgs a;
     a.r.pts = frame_pts; a.r.foff = frame_off; a.r.dets = dets; a.r.crow = cand_row; a.r.cframe = cand_frame; a.r.ooff = nullptr;
@@ -367,4 +388,25 @@ extern "C" int fcn_refine_label_fill(const float *frame_pts, const int64_t *fram
         hipLaunchKernelGGL(rl_fill_kernel<false>, dim3(S, D * A), dim3(FS_T), 0, (hipStream_t)stream, a);
     FCN_CHECK_LAUNCH();
     return (ok && ok_gt) ? 0 : FCN_E_BADARG;
+}
+
+extern "C" int fcn_refine_label_count(const float *frame_pts, const int64_t *frame_off, int F, int pt_stride, const float *dets,
+                                      int R, const int32_t *cand_row, const int32_t *cand_frame, int D, double ratio,
+                                      const int32_t *cand_gt, const double *gt_box3d, int G, int A, const double *jitter,
+                                      double shift_ratio, int S, int32_t *seg_cnt, int32_t *seg_pos, double *pred_corners,
+                                      double *pred_angle, double *pred_size, double *gt_corners, double *gt_heading,
+                                      double *gt_size, void *stream)
+{
+    return rl_count_launch(frame_pts, frame_off, F, pt_stride, dets, R, cand_row, cand_frame, D, ratio, cand_gt, gt_box3d, G, A, jitter,
+                           shift_ratio, S, seg_cnt, seg_pos, pred_corners, pred_angle, pred_size, gt_corners, gt_heading, gt_size,
+                           stream, true);
+}
+
+extern "C" int fcn_refine_label_fill(const float *frame_pts, const int64_t *frame_off, int F, int pt_stride, const float *dets,
+                                     int R, const int32_t *cand_row, const int32_t *cand_frame, int D, double ratio,
+                                     const int32_t *cand_gt, const double *gt_box3d, int G, int A, const double *jitter,
+                                     double shift_ratio, int S, const int64_t *seg_off, float *out_pts, void *stream)
+{
+    return rl_fill_launch(frame_pts, frame_off, F, pt_stride, dets, R, cand_row, cand_frame, D, ratio, cand_gt, gt_box3d, G, A, jitter,
+                          shift_ratio, S, seg_off, out_pts, stream, true);
 }

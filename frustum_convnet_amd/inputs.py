@@ -606,34 +606,49 @@ class RefineInputBuilder:
             raise NotImplementedError("RefineInputBuilder implements the cfg.DATA.RTC = True geometry only (every shipped "
                                       "refine cfg sets it: cfgs/refine_car.yaml, cfgs/refine_people.yaml)")
 
-    def _launch(self, t, B, pt_stride, Lpad, with_labels):
-        """Allocates the outputs and enqueues fcn_prepare_inputs_refine on the device tensors `t` (raw, off, choice, pcorners,
-        pangle, psize; with labels also corners, heading, size, coin, normal): the part build() and build_device() share."""
-        from ._native import InpRefineDesc
+    def alloc(self, B, lpad, with_labels=True):
+        """Output tensors of launch() for a batch of B samples at the padded window counts lpad (four ints), zero-filled (pass as
+        `out` to write the same buffers every step)."""
         dev, N = self.device, self.npoints
         f32 = dict(dtype=torch.float32, device=dev)
-        out = {"point_cloud": torch.empty((B, 3, N), **f32), "rot_angle": torch.empty((B, 1), **f32),
-               "ref_center": torch.empty((B, 3), **f32), "lens": torch.empty((B, 4), dtype=torch.int32, device=dev)}
+        out = {"point_cloud": torch.zeros((B, 3, N), **f32), "rot_angle": torch.zeros((B, 1), **f32),
+               "ref_center": torch.zeros((B, 3), **f32), "lens": torch.zeros((B, 4), dtype=torch.int32, device=dev)}
         if with_labels:
-            out.update(cls_label=torch.empty((B, Lpad[1]), dtype=torch.int64, device=dev),
-                       box3d_center=torch.empty((B, 3), **f32), box3d_heading=torch.empty((B, 1), **f32),
-                       box3d_size=torch.empty((B, 3), **f32))
+            out.update(cls_label=torch.zeros((B, lpad[1]), dtype=torch.int64, device=dev),
+                       box3d_center=torch.zeros((B, 3), **f32), box3d_heading=torch.zeros((B, 1), **f32),
+                       box3d_size=torch.zeros((B, 3), **f32))
         for s in range(4):
-            out["center_ref%d" % (s + 1)] = torch.empty((B, 3, Lpad[s]), **f32)
-        desc = InpRefineDesc(B, N, pt_stride, (ctypes.c_int32 * 4)(*Lpad), (ctypes.c_double * 4)(*self.strides),
+            out["center_ref%d" % (s + 1)] = torch.zeros((B, 3, lpad[s]), **f32)
+        return out
+
+    def launch(self, t, out, pt_stride, lpad, with_labels=True):
+        """ONE launch of fcn_prepare_inputs_refine on the current stream: the device tensors `t` (raw, off, choice, pcorners, pangle,
+        psize; with labels also corners, heading, size, coin, normal) -> `out` (alloc(B, lpad, with_labels)).  No allocation, no
+        host read: capturable into a hipGraph.  Returns `out`."""
+        from ._native import InpRefineDesc
+        dev = self.device
+        B = int(out["point_cloud"].shape[0])
+        desc = InpRefineDesc(B, self.npoints, pt_stride, (ctypes.c_int32 * 4)(*lpad), (ctypes.c_double * 4)(*self.strides),
                              1 if (self.random_flip and with_labels) else 0, 1 if (self.random_shift and with_labels) else 0)
         refs = (ctypes.c_void_p * 4)(*[out["center_ref%d" % (s + 1)].data_ptr() for s in range(4)])
         p = lambda x: None if x is None else x.data_ptr()
+        lab = (lambda k: p(t.get(k))) if with_labels else (lambda k: None)
+        olab = (lambda k: p(out.get(k))) if with_labels else (lambda k: None)
         L = _native.lib()
         with torch.cuda.device(dev):
             _native.check(L.fcn_prepare_inputs_refine(
                 ctypes.byref(desc), p(t["raw"]), p(t["off"]), p(t["choice"]), p(t["pcorners"]), p(t["pangle"]), p(t["psize"]),
-                p(t.get("corners")), p(t.get("heading")), p(t.get("size")), p(t.get("coin")), p(t.get("normal")),
-                p(out["point_cloud"]), refs, p(out.get("cls_label")), p(out.get("box3d_center")), p(out.get("box3d_heading")),
-                p(out.get("box3d_size")), p(out["rot_angle"]), p(out["ref_center"]), p(out["lens"]),
+                lab("corners"), lab("heading"), lab("size"), lab("coin"), lab("normal"),
+                p(out["point_cloud"]), refs, olab("cls_label"), olab("box3d_center"), olab("box3d_heading"),
+                olab("box3d_size"), p(out["rot_angle"]), p(out["ref_center"]), p(out["lens"]),
                 _native.current_stream(dev)), "fcn_prepare_inputs_refine")
+        return out
+
+    def _launch(self, t, B, pt_stride, Lpad, with_labels):
+        """alloc() + launch() on the device tensors `t`: the part build(), build_device() and build_device_train() share."""
+        out = self.launch(t, self.alloc(B, Lpad, with_labels), pt_stride, Lpad, with_labels)
         for v in t.values():
-            v.record_stream(torch.cuda.current_stream(dev))
+            v.record_stream(torch.cuda.current_stream(self.device))
         return out
 
     def _lpad(self, widths):

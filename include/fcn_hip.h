@@ -982,7 +982,8 @@ int fcn_draw_batch_sliced(const fcn_draw_desc *d, const int64_t *counts, const i
  * pointers, pt_stride < 3, S < 1, A out of range, NULL jitter with A != 1, D * A > 65535 and a frame longer than S * seg rows are
  * FCN_E_BADARG with no launch.  A candidate whose row or frame is out of range, or whose cand_gt >= G, is never dereferenced: its
  * counts are 0 (match: gt_idx = -1), nothing else of it is written, the others are processed and the call returns FCN_E_BADARG.
- * All three calls read their index lists back first (a stream synchronisation: NOT capturable into a hipGraph). */
+ * All three calls read their index lists back first (a stream synchronisation: NOT capturable into a hipGraph; the capturable
+ * forms are fcn_refine_train_match / _count / _fill below). */
 int fcn_refine_match(const float *dets, int R, const int32_t *cand_row, const int32_t *cand_frame, int D, const double *gt_box3d,
                      int G, const int64_t *gt_off, int F, double thresh, int32_t *gt_idx, float *best_iou, void *stream);
 int fcn_refine_label_count(const float *frame_pts, const int64_t *frame_off, int F, int pt_stride, const float *dets, int R,
@@ -994,6 +995,58 @@ int fcn_refine_label_fill(const float *frame_pts, const int64_t *frame_off, int 
                           const int32_t *cand_row, const int32_t *cand_frame, int D, double ratio, const int32_t *cand_gt,
                           const double *gt_box3d, int G, int A, const double *jitter, double shift_ratio, int S,
                           const int64_t *seg_off, float *out_pts, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * The refinement stage's training input with no host read between its launches (csrc/refine_plan.h; INTEGRATION.md "Capturable
+ * refine-stage training input" states the contract bit for bit, tests/refine_plan_ref.py restates it in numpy): match, jitter
+ * draw, count, plan, fill -- none of them reads anything back, allocates or synchronises, so the sequence can be captured into a
+ * hipGraph.  Status bits (*status: one int32 on the device, OR-ed, never cleared here): bit 1 (2) fewer than B surviving units;
+ * bit 2 (4) rows dropped because the total exceeds `capacity`; bit 5 (32) a unit with positives whose predicted width needs more
+ * windows than lpad on some stride; bit 6 (64) a unit with positives whose predicted width is not a positive finite number.
+ * (Bit 0 is fcn_draw_batch's.)
+ *
+ * fcn_refine_train_match / _count / _fill: fcn_refine_match, fcn_refine_label_count / _fill without the read-back of cand_row,
+ * cand_frame, cand_gt and frame_off: the same kernels, arguments, outputs and argument refusals.  A candidate whose row or frame is
+ * out of range, or whose cand_gt >= G, is skipped as there (its counts are 0; match: gt_idx = -1, best_iou = 0; nothing of it is
+ * dereferenced) but NOT reported: the calls return 0.  "No frame is longer than S * fcn_frustum_select_seg() rows" is the caller's
+ * duty: rows beyond S segments would silently not be searched. */
+int fcn_refine_train_match(const float *dets, int R, const int32_t *cand_row, const int32_t *cand_frame, int D,
+                           const double *gt_box3d, int G, const int64_t *gt_off, int F, double thresh, int32_t *gt_idx,
+                           float *best_iou, void *stream);
+int fcn_refine_train_count(const float *frame_pts, const int64_t *frame_off, int F, int pt_stride, const float *dets, int R,
+                           const int32_t *cand_row, const int32_t *cand_frame, int D, double ratio, const int32_t *cand_gt,
+                           const double *gt_box3d, int G, int A, const double *jitter, double shift_ratio, int S,
+                           int32_t *seg_cnt, int32_t *seg_pos, double *pred_corners, double *pred_angle, double *pred_size,
+                           double *gt_corners, double *gt_heading, double *gt_size, void *stream);
+int fcn_refine_train_fill(const float *frame_pts, const int64_t *frame_off, int F, int pt_stride, const float *dets, int R,
+                          const int32_t *cand_row, const int32_t *cand_frame, int D, double ratio, const int32_t *cand_gt,
+                          const double *gt_box3d, int G, int A, const double *jitter, double shift_ratio, int S,
+                          const int64_t *seg_off, float *out_pts, void *stream);
+/* fcn_box3d_jitter_draw: the (D,A,7) fp64 uniforms in [0,1) that fcn_refine_label_count / fcn_refine_train_count take as `jitter`,
+ * for every unit u = d * A + a, one lane per unit.  Philox4x32-10 as fcn_draw_batch keys it, counter (block, u, step lo,
+ * ((step >> 32) << 2) | 3), step = state[0]: blocks 0..3 give words w0..w15, uniform j = u53(w[2j], w[2j+1]) * 2^-53 for
+ * j = 0..6 in the reference's order l, h, w, cx, cy, cz, angle (u53(hi, lo) = (hi >> 5) * 2^26 + (lo >> 6)); words 14 and 15 are
+ * unused.  advance != 0: a one-thread launch behind the kernel leaves state[0] + 1.  D == 0 writes nothing (apart from the advance).
+ * NULL pointers, D < 0, A < 1 or A > 64: FCN_E_BADARG; D * A > 65535: FCN_E_LIMIT; nothing written. */
+int fcn_box3d_jitter_draw(int D, int A, uint64_t seed, const int64_t *state, int advance, double *jitter, void *stream);
+/* fcn_refine_train_plan: what the host does between count and fill, as one workgroup.  seg_cnt, seg_pos (U,S) int32 and pred_size
+ * (U,3) fp64 from the count; stride[4] fp64 and lpad[4] int32 (host arrays): the builder's strides and the FIXED padded window
+ * counts of the batch.  A unit with sum_s seg_pos == 0 takes no slot and no room (the reject rule, :547; it covers the units of
+ * unmatched candidates, whose rows of pred_size the count never wrote: pred_size[u] is read only when unit u has a positive).  For
+ * a unit with a positive, w = pred_size[3u + 1]: !(w > 0 and finite) -> no slot, bit 6; else ceil((w / 2 - (-w / 2)) / stride[s]) >
+ * lpad[s] on any stride (fcn_prepare_inputs_refine's own expression, compared in fp64) -> no slot, bit 5.  The first B surviving
+ * units in unit order take slots 0..n-1: slot_unit (B) int32 their unit, U for an empty slot (the spare row of the caller's
+ * per-unit tables), *n_kept = n.  seg_off (U*S+1) int64 = min(capacity, the exclusive prefix sum over the flattened segments of
+ * seg_cnt where the unit holds a slot, else 0), the last entry the clamped total: what the fill takes.  off (B+1) int64: off[i] =
+ * seg_off[slot_unit[i] * S] for i < n, `capacity` for n <= i < B (the spare row of a point buffer of capacity + 1 rows, which the
+ * fill never stores), off[B] the clamped total.  counts (B) int64: the STORED rows of each slot, seg_off[(u+1)*S] - seg_off[u*S],
+ * 0 for an empty slot.  n < B sets bit 1, a total above capacity bit 2.  Every output is written on every call.
+ * NULL pointers, U < 0, S < 1, B < 1, capacity < 0, an lpad[s] < 1 or !(stride[s] > 0): FCN_E_BADARG; U or B > 2048 or U * S > 65536
+ * (fcn_refine_train_plan_limits): FCN_E_LIMIT; nothing written. */
+int fcn_refine_train_plan(const int32_t *seg_cnt, const int32_t *seg_pos, const double *pred_size, const double *stride,
+                          const int32_t *lpad, int U, int S, int B, int64_t capacity, int32_t *slot_unit, int32_t *n_kept,
+                          int64_t *seg_off, int64_t *off, int64_t *counts, int32_t *status, void *stream);
+int fcn_refine_train_plan_limits(int *max_u, int *max_segs);
 
 #ifdef __cplusplus
 }
