@@ -22,6 +22,7 @@ import torch
 
 from . import _native
 from .detect import _need_cuda
+from .frustum import _frames
 
 
 def refine_candidates(frame_points, frame_off, dets, cand_row, cand_frame, ratio=1.2):
@@ -33,12 +34,8 @@ def refine_candidates(frame_points, frame_off, dets, cand_row, cand_frame, ratio
     off (D+1) int64; pred_box3d (D,8,3), pred_angle (D), pred_size (D,3) fp64 (the enlarged box: corners in the order of
     compute_box_3d_obj_array, ry, l/w/h); cnt (D) int32; score (D) float32 (column 7 of the candidates' rows) -- on the device --
     and counts (D) int64 on the host: the one read between the two launches."""
-    _need_cuda(frame_points, "refine_candidates")
+    pts, foff, F, ps, _ = _frames("refine_candidates", frame_points, frame_off)       # (one workgroup per box: no segments)
     dev = frame_points.device
-    pts = frame_points.detach().contiguous().float()
-    if pts.dim() != 2 or pts.shape[1] < 3:
-        raise ValueError("refine_candidates: frame_points must be (n, >= 3), got %s" % (tuple(frame_points.shape),))
-    foff = torch.as_tensor(frame_off).to(device=dev, dtype=torch.int64).contiguous()
     d8 = dets.detach().to(device=dev, dtype=torch.float32).contiguous()
     if d8.dim() != 2 or d8.shape[1] != 8:
         raise ValueError("refine_candidates: dets must be (R, 8), got %s" % (tuple(dets.shape),))
@@ -46,7 +43,7 @@ def refine_candidates(frame_points, frame_off, dets, cand_row, cand_frame, ratio
     cframe = torch.as_tensor(cand_frame).to(device=dev, dtype=torch.int32).contiguous().view(-1)
     if crow.numel() != cframe.numel():
         raise ValueError("refine_candidates: %d rows but %d frames" % (crow.numel(), cframe.numel()))
-    F, R, D, ps = int(foff.numel()) - 1, int(d8.shape[0]), int(crow.numel()), int(pts.shape[1])
+    R, D = int(d8.shape[0]), int(crow.numel())
     f64 = dict(dtype=torch.float64, device=dev)
     out = {"pred_box3d": torch.zeros((D, 8, 3), **f64), "pred_angle": torch.zeros((D,), **f64),
            "pred_size": torch.zeros((D, 3), **f64), "cnt": torch.zeros((D,), dtype=torch.int32, device=dev)}
@@ -134,17 +131,12 @@ def refine_training_candidates(frame_points, frame_off, dets, cand_row, cand_fra
     (K) int64 on the host.  With no kept unit the dict holds 'kept' alone.
     The host reads the 2 * U * S selected and positive segment counts once, together, between the two launches."""
     who = "refine_training_candidates"
-    _need_cuda(frame_points, who)
+    pts, foff, F, ps, S = _frames(who, frame_points, frame_off)
     dev = frame_points.device
-    pts = frame_points.detach().contiguous().float()
-    if pts.dim() != 2 or pts.shape[1] < 3:
-        raise ValueError("%s: frame_points must be (n, >= 3), got %s" % (who, tuple(frame_points.shape)))
-    foff_h = torch.as_tensor(frame_off).detach().cpu().to(torch.int64).contiguous().view(-1)      # F + 1 integers: they decide S
-    foff = foff_h.to(dev, non_blocking=True)
     d8, crow, cframe = _candidates(who, frame_points, dets, cand_row, cand_frame)
     cgt = torch.as_tensor(cand_gt).to(device=dev, dtype=torch.int32).contiguous().view(-1)
     gt = torch.as_tensor(gt_box3d).to(device=dev, dtype=torch.float64).contiguous().view(-1, 7)
-    F, R, D, G, ps = int(foff_h.numel()) - 1, int(d8.shape[0]), int(crow.numel()), int(gt.shape[0]), int(pts.shape[1])
+    R, D, G = int(d8.shape[0]), int(crow.numel()), int(gt.shape[0])
     if cgt.numel() != D:
         raise ValueError("%s: %d candidates but %d cand_gt" % (who, D, cgt.numel()))
     A, jit = 1, None
@@ -158,10 +150,6 @@ def refine_training_candidates(frame_points, frame_off, dets, cand_row, cand_fra
         return none
     U = D * A
     L = _native.lib()
-    seg = int(L.fcn_frustum_select_seg())
-    S = max(1, -(-int((foff_h[1:] - foff_h[:-1]).max()) // seg))
-    if pts.shape[0] == 0:
-        pts = torch.zeros((1, ps), dtype=torch.float32, device=dev)        # (an address to hand in: every frame is empty)
     f64 = dict(dtype=torch.float64, device=dev)
     pc, pa, psz = torch.zeros((U, 8, 3), **f64), torch.zeros((U,), **f64), torch.zeros((U, 3), **f64)
     gc, gh, gs = torch.zeros((U, 8, 3), **f64), torch.zeros((U,), **f64), torch.zeros((U, 3), **f64)
@@ -224,20 +212,9 @@ class RefineTrainSource:
                  seed, thresh=0.5, ratio=1.2, shift_ratio=0.05, pick=True, jitter=True):
         from .inputs import DeviceDraws
         who = "RefineTrainSource"
-        _need_cuda(frame_points, who)
+        pts, foff, F, ps, S = _frames(who, frame_points, frame_off, resident=True)
         dev = frame_points.device
         L = _native.lib()
-        pts = frame_points.detach().contiguous().float()
-        if pts.dim() != 2 or pts.shape[1] < 3:
-            raise ValueError("%s: frame_points must be (n, >= 3), got %s" % (who, tuple(frame_points.shape)))
-        foff_h = torch.as_tensor(frame_off).detach().cpu().to(torch.int64).contiguous().view(-1).numpy()
-        F, ps = len(foff_h) - 1, int(pts.shape[1])
-        if F < 1 or foff_h[0] < 0 or (np.diff(foff_h) < 0).any() or foff_h[-1] > pts.shape[0]:
-            raise ValueError("%s: frame_off must be F + 1 >= 2 ascending row offsets into the %d rows" % (who, pts.shape[0]))
-        seg = int(L.fcn_frustum_select_seg())
-        S = max(1, -(-int(np.diff(foff_h).max()) // seg))       # no frame is longer than S segments: checked HERE, once
-        if pts.shape[0] == 0:
-            pts = torch.zeros((1, ps), dtype=torch.float32, device=dev)
         if not (isinstance(dets, torch.Tensor) and dets.is_cuda and dets.dtype == torch.float32 and dets.is_contiguous()
                 and dets.dim() == 2 and dets.shape[1] == 8 and not dets.requires_grad):
             raise ValueError("%s: dets must be a contiguous (R, 8) float32 device tensor (it is held, not copied)" % who)
@@ -297,7 +274,7 @@ class RefineTrainSource:
         f64, i32, i64 = (dict(dtype=t, device=dev) for t in (torch.float64, torch.int32, torch.int64))
         N = builder.npoints
         # ---- resident: the frames, the detections (held), the labels
-        self.frames = (pts, up(foff_h))
+        self.frames = (pts, foff)
         self.dets = dets
         self.det_frame, self.det_class = up(dfr.astype(np.int32)), up(np.asarray(cls, dtype=np.int64).reshape(R, 1))
         self.gt, self.gt_off = up(gt), up(goff_h)

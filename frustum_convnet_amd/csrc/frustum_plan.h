@@ -5,7 +5,7 @@
 // restates it in numpy):
 //   fcn_box2d_perturb          kitti/prepare_data.py::random_shift_box2d (:55-77) for D boxes, one lane per box, on the counter-based
 //                              stream of draws.h (tag 3, the one tag fcn_draw_batch leaves free), with a BOUNDED retry;
-//   fcn_frustum_train_count    fl_count_kernel / fl_fill_kernel of frustum_label.h as they are, launched without fs_read_lists: the
+//   fcn_frustum_train_count    the count / fill of frustum_label.h (seg_compact.h with FlSelect), launched without a read-back: the
 //   fcn_frustum_train_fill     kernels skip a box whose frame is out of range; "no frame longer than S * FS_SEG rows" is the caller's
 //                              duty (checked once, where the frames are made resident);
 //   fcn_frustum_train_plan     ONE workgroup between the two: the reject rule per box, the first B survivors IN BOX ORDER -> slots,

@@ -3,36 +3,31 @@
 // upright CAMERA coordinates (with their foreground labels and the box corners), on the device.  The reference does this on the
 // host in numpy, scanning the whole frame once per box (sunrgbd/prepare_data.py::extract_frustum_data :132-267,
 // extract_frustum_data_from_rgb_detection :270-381 with sunrgbd_utils.SUNRGBD_Calibration).  Here it is the two launches of
-// frustum_select.h over the same grid of (S, D) workgroups, with the same segments, quarters and ballot + prefix-popcount
-// compaction -- fs_quarter, fs_finite, fs_read_lists, FS_T, FS_SEG and FS_MAX_D are used as they stand; only the geometry is new:
-//   sr_count_kernel   seg_cnt[d * S + s] (and, labelled, seg_pos[d * S + s]); workgroup s == 0 also writes the frustum angle of
-//                     the box centre (and the eight corners in compute_box_3d's order, flipped to upright camera);
-//   sr_fill_kernel    after the caller's cumulative sum over the (D * S) counts: the selected rows in ascending frame order as
-//                     (x, -z, y) of the input row -- an exact swap and negation -- then columns 3.. bit for bit (and out_seg).
+// seg_compact.h over a grid of (S, D) workgroups; only the geometry is new (SrSelect<LAB>, LAB: with the label box):
+//   count   seg_cnt[d * S + s] (and, labelled, seg_pos[d * S + s]); workgroup s == 0 also writes the frustum angle of the box
+//           centre (and the eight corners in compute_box_3d's order, flipped to upright camera);
+//   fill    after the caller's cumulative sum over the (D * S) counts: the selected rows in ascending frame order as (x, -z, y) of
+//           the input row -- an exact swap and negation -- then columns 3.. bit for bit (and out_seg).
 // ONE selection predicate (sr_select), in fp64 from the fp32 row, every sum left to right (-ffp-contract=off):
 //   d = Rtilt^T . (x, y, z), c = (d0, -d2, d1), i = K . c, u = i0 / i2, v = i1 / i2; selected iff xmin <= u < xmax, ymin <= v < ymax.
 // No image-bounds test, no clip distance, no guard on i2: the reference has none (:191-192).  A row with a non-finite x, y or z is
 // never selected.  Boxes are used as given.
 // ONE in-box predicate (sr_inside), closed, on the input row in upright depth: with c = cos(-heading), s = sin(-heading),
 // dx = x - cx, dy = y - cy, dz = z - cz: ax = c * dx + s * dy, ay = -s * dx + c * dy; inside iff |ax| <= l, |ay| <= w, |dz| <= h
-// (l, w, h are the label file's HALF extents).  No workgroup waits for another; there are no atomics.
+// (l, w, h are the label file's HALF extents).
 #pragma once
 #include "frustum_select.h"
 
 struct SrArgs {
-    const float *pts;                  // (sum m_f, ps) upright depth x, y, z, then r, g, b, ...
+    ScArgs c;                          // c.pts: (sum m_f, ps) upright depth x, y, z, then r, g, b, ...
     const int64_t *foff;               // (F+1)
     const double *K, *Rt;              // (F,9) (F,9) row-major
     const double *boxes;               // (D,4)
     const int32_t *bframe;             // (D)
     const double *gt;                  // (D,7) cx cy cz l w h heading, labelled only
-    const int64_t *soff;               // (D*S+1), fill only
-    int F, ps, D, S;
+    int F;
     double *angle;                     // count only
-    int32_t *scnt, *spos;              // count only (spos labelled only)
     double *corners;                   // (D,24), labelled count only
-    float *out;                        // fill only
-    int64_t *oseg;                     // labelled fill only
 };
 
 struct SrBox {
@@ -69,7 +64,7 @@ __device__ __forceinline__ void sr_gt(const SrArgs &a, int d, SrGt &g)
 // THE selection predicate of both kernels
 __device__ __forceinline__ bool sr_select(const SrBox &b, float xf, float yf, float zf)
 {
-    if (!(fs_finite(xf) && fs_finite(yf) && fs_finite(zf))) return false;
+    if (!(sc_finite(xf) && sc_finite(yf) && sc_finite(zf))) return false;
     const double x = xf, y = yf, z = zf;
     const double d0 = b.r[0] * x + b.r[3] * y + b.r[6] * z;               // Rtilt^T
     const double d1 = b.r[1] * x + b.r[4] * y + b.r[7] * z;
@@ -89,18 +84,6 @@ __device__ __forceinline__ bool sr_inside(const SrGt &g, float xf, float yf, flo
     const double ax = g.c * dx + g.s * dy;
     const double ay = (-g.s) * dx + g.c * dy;
     return fabs(ax) <= g.l && fabs(ay) <= g.w && fabs(dz) <= g.h;
-}
-
-// V4: pt_stride == 4 and 16-byte aligned rows -- one 16-byte load per point.  v: the INPUT row's first four floats
-template <bool V4> __device__ __forceinline__ bool sr_test(const SrArgs &a, const SrBox &b, int64_t row, float4 &v)
-{
-    if constexpr (V4) {
-        v = *(const float4 *)(a.pts + row * 4);
-    } else {
-        const float *p = a.pts + row * a.ps;
-        v.x = p[0]; v.y = p[1]; v.z = p[2]; v.w = 0.f;
-    }
-    return sr_select(b, v.x, v.y, v.z);
 }
 
 // project_image_to_upright_camera of (box centre, depth 20) -> -atan2(z, x) of the upright camera point
@@ -129,162 +112,73 @@ __device__ __forceinline__ void sr_corners(const SrGt &g, double *o)
     }
 }
 
-template <bool V4, bool LAB> __global__ __launch_bounds__(FS_T) void sr_count_kernel(SrArgs a)
-{
-    __shared__ int wcnt[FS_WAVES], wpos[FS_WAVES];
-    const int s = blockIdx.x, d = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+template <bool LAB> struct SrSelect {
+    using Args = SrArgs;
+    static constexpr bool WHOLE = false, POS = LAB, SEG = LAB;
     SrBox b;
-    int64_t p0, m;
-    if (!sr_setup(a, d, b, p0, m)) {           // (workgroup-uniform)
-        if (tid == 0) {
-            a.scnt[(int64_t)d * a.S + s] = 0;
-            if constexpr (LAB) a.spos[(int64_t)d * a.S + s] = 0;
-        }
-        return;
+    SrGt g;
+    __device__ __forceinline__ bool setup(const SrArgs &a, int d, int64_t &p0, int64_t &m)
+    {
+        if (!sr_setup(a, d, b, p0, m)) return false;
+        if constexpr (LAB) sr_gt(a, d, g);
+        return true;
     }
-    SrGt g = {};
-    if constexpr (LAB) sr_gt(a, d, g);
-    if (s == 0 && tid == 0) {
+    __device__ __forceinline__ void header(const SrArgs &a, int d, int tid) const
+    {
+        if (tid != 0) return;
         a.angle[d] = sr_angle(b);
         if constexpr (LAB) sr_corners(g, a.corners + (int64_t)d * 24);
     }
-    int64_t lo, hi;
-    fs_quarter(m, s, wave, lo, hi);
-    int c = 0, p = 0;
-    float4 v;
-    for (int64_t i = lo + lane; i < hi; i += 64)
-        if (sr_test<V4>(a, b, p0 + i, v)) {
-            c += 1;
-            if constexpr (LAB) p += sr_inside(g, v.x, v.y, v.z) ? 1 : 0;
-        }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { c += __shfl_xor(c, o, 64); p += __shfl_xor(p, o, 64); }
-    if (lane == 0) { wcnt[wave] = c; wpos[wave] = p; }
-    __syncthreads();
-    if (tid == 0) {
-        int tc = 0, tp = 0;
-        for (int w = 0; w < FS_WAVES; ++w) { tc += wcnt[w]; tp += wpos[w]; }
-        a.scnt[(int64_t)d * a.S + s] = tc;
-        if constexpr (LAB) a.spos[(int64_t)d * a.S + s] = tp;
+    __device__ __forceinline__ bool select(const float4 &v, float4 &o) const
+    {
+        o = make_float4(v.x, -v.z, v.y, v.w);  // upright depth -> upright camera: (x, -z, y), the xyz bits are the input's
+        return sr_select(b, v.x, v.y, v.z);
     }
-}
+    __device__ __forceinline__ bool positive(const float4 &v, const float4 &) const { return sr_inside(g, v.x, v.y, v.z); }
+};
 
-template <bool V4, bool LAB> __global__ __launch_bounds__(FS_T) void sr_fill_kernel(SrArgs a)
-{
-    __shared__ int wcnt[FS_WAVES];
-    const int s = blockIdx.x, d = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    SrBox b;
-    int64_t p0, m;
-    if (!sr_setup(a, d, b, p0, m)) return;
-    SrGt g = {};
-    if constexpr (LAB) sr_gt(a, d, g);
-    int64_t lo, hi;
-    fs_quarter(m, s, wave, lo, hi);
-    int c = 0;
-    float4 v;
-    for (int64_t i = lo + lane; i < hi; i += 64) c += sr_test<V4>(a, b, p0 + i, v) ? 1 : 0;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
-    if (lane == 0) wcnt[wave] = c;
-    __syncthreads();
-    int64_t run = 0;
-    for (int w = 0; w < wave; ++w) run += wcnt[w];
-    // the caller's offsets bound BOTH stores: a row beyond this workgroup's slice is dropped from out_pts and out_seg alike
-    const int64_t o0 = a.soff[(int64_t)d * a.S + s];
-    int64_t cap = a.soff[(int64_t)d * a.S + s + 1] - o0;
-    if (o0 < 0) cap = 0;
-    const unsigned long long lt_mask = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
-    for (int64_t i0 = lo; i0 < hi; i0 += 64) {
-        const int64_t i = i0 + lane;
-        const bool in = i < hi && sr_test<V4>(a, b, p0 + i, v);
-        const unsigned long long mask = __ballot(in);
-        if (mask == 0ull) continue;
-        const int64_t pos = run + (int64_t)__popcll(mask & lt_mask);
-        if (in && pos < cap) {
-            // upright depth -> upright camera: (x, -z, y), the xyz bits are the input's
-            if constexpr (V4) {
-                *(float4 *)(a.out + (o0 + pos) * 4) = make_float4(v.x, -v.z, v.y, v.w);
-            } else {
-                const uint32_t *src = (const uint32_t *)(a.pts + (p0 + i) * a.ps);
-                float *dst = a.out + (o0 + pos) * a.ps;
-                dst[0] = v.x; dst[1] = -v.z; dst[2] = v.y;
-                for (int k = 3; k < a.ps; ++k) ((uint32_t *)dst)[k] = src[k];
-            }
-            if constexpr (LAB) a.oseg[o0 + pos] = sr_inside(g, v.x, v.y, v.z) ? 1 : 0;
-        }
-        run += (int64_t)__popcll(mask);
-    }
-}
-
-// what the four entry points share: the refusals of frustum_select.h, then the launch.  count: scnt != nullptr
-// read_lists: read box_frame and frame_off back first (fs_read_lists: a synchronisation) and report an out-of-range frame or a frame
-// longer than S segments; without it (the no-read pair of frustum_sunrgbd_plan.h) nothing is read and 0 is returned once the launch
-// is enqueued -- the kernels skip a box whose frame is out of range either way, the length condition is the caller's then.
-static inline int sr_launch(SrArgs &a, bool fill, bool lab, hipStream_t stream, bool read_lists = true)
-{
-    bool ok = true, fits = true;
-    if (read_lists) {
-        ok = false; fits = false;
-        FCN_TRY(fs_read_lists(a.bframe, a.foff, a.D, a.F, a.S, stream, &ok, &fits));
-    }
-    if (!fits) return FCN_E_BADARG;
-    const bool v4 = fs_vec4(a.pts, fill ? a.out : nullptr, a.ps);
-    const dim3 grid(a.S, a.D), block(FS_T);
-    if (!fill) {
-        if (lab) {
-            if (v4) hipLaunchKernelGGL((sr_count_kernel<true, true>), grid, block, 0, stream, a);
-            else hipLaunchKernelGGL((sr_count_kernel<false, true>), grid, block, 0, stream, a);
-        } else {
-            if (v4) hipLaunchKernelGGL((sr_count_kernel<true, false>), grid, block, 0, stream, a);
-            else hipLaunchKernelGGL((sr_count_kernel<false, false>), grid, block, 0, stream, a);
-        }
-    } else {
-        if (lab) {
-            if (v4) hipLaunchKernelGGL((sr_fill_kernel<true, true>), grid, block, 0, stream, a);
-            else hipLaunchKernelGGL((sr_fill_kernel<false, true>), grid, block, 0, stream, a);
-        } else {
-            if (v4) hipLaunchKernelGGL((sr_fill_kernel<true, false>), grid, block, 0, stream, a);
-            else hipLaunchKernelGGL((sr_fill_kernel<false, false>), grid, block, 0, stream, a);
-        }
-    }
-    FCN_CHECK_LAUNCH();
-    return ok ? 0 : FCN_E_BADARG;
-}
-
+// what the four entry points share after the refusals of frustum_select.h: the kernels' arguments and the launch (sc_launch;
+// read_lists = false is the no-read pair of frustum_sunrgbd_plan.h)
 static inline void sr_args(SrArgs &a, const float *frame_pts, const int64_t *frame_off, int F, int pt_stride, const double *K,
-                           const double *Rtilt, const double *boxes, const int32_t *box_frame, int D, int S)
+                           const double *Rtilt, const double *boxes, const int32_t *box_frame, int S)
 {
-    a.pts = frame_pts; a.foff = frame_off; a.K = K; a.Rt = Rtilt; a.boxes = boxes; a.bframe = box_frame; a.gt = nullptr;
-    a.soff = nullptr; a.F = F; a.ps = pt_stride; a.D = D; a.S = S; a.angle = nullptr; a.scnt = nullptr; a.spos = nullptr;
-    a.corners = nullptr; a.out = nullptr; a.oseg = nullptr;
+    a = SrArgs();
+    a.c.pts = frame_pts; a.c.ps = pt_stride; a.c.S = S;
+    a.foff = frame_off; a.K = K; a.Rt = Rtilt; a.boxes = boxes; a.bframe = box_frame; a.F = F;
+}
+
+template <bool LAB, bool FILL> static inline int sr_launch(const SrArgs &a, int D, hipStream_t stream, bool read_lists)
+{
+    const ScList lists[1] = {{a.bframe, a.F, false}};
+    return sc_launch<SrSelect<LAB>, FILL>(a, D, lists, 1, D, a.foff, a.F, stream, read_lists);
 }
 
 extern "C" int fcn_frustum_sunrgbd_count(const float *frame_pts, const int64_t *frame_off, int F, int pt_stride, const double *K,
                                          const double *Rtilt, const double *boxes, const int32_t *box_frame, int D, int S,
                                          double *frustum_angle, int32_t *seg_cnt, void *stream)
 {
-    if (pt_stride < 3 || D < 0 || F < 0 || S < 1 || D > FS_MAX_D) return FCN_E_BADARG;
+    if (!fs_sizes_ok(F, pt_stride, D, S)) return FCN_E_BADARG;
     if (D == 0) return 0;
     if (!seg_cnt) return FCN_E_BADARG;
-    if (F == 0) return (int)hipMemsetAsync(seg_cnt, 0, (size_t)D * S * sizeof(int32_t), (hipStream_t)stream);
+    if (F == 0) return sc_zero_counts(seg_cnt, nullptr, (size_t)D * S, (hipStream_t)stream);
     if (!frame_pts || !frame_off || !K || !Rtilt || !boxes || !box_frame || !frustum_angle) return FCN_E_BADARG;
     SrArgs a;
-    sr_args(a, frame_pts, frame_off, F, pt_stride, K, Rtilt, boxes, box_frame, D, S);
-    a.angle = frustum_angle; a.scnt = seg_cnt;
-    return sr_launch(a, false, false, (hipStream_t)stream);
+    sr_args(a, frame_pts, frame_off, F, pt_stride, K, Rtilt, boxes, box_frame, S);
+    a.angle = frustum_angle; a.c.scnt = seg_cnt;
+    return sr_launch<false, false>(a, D, (hipStream_t)stream, true);
 }
 
 extern "C" int fcn_frustum_sunrgbd_fill(const float *frame_pts, const int64_t *frame_off, int F, int pt_stride, const double *K,
                                         const double *Rtilt, const double *boxes, const int32_t *box_frame, int D, int S,
                                         const int64_t *seg_off, float *out_pts, void *stream)
 {
-    if (pt_stride < 3 || D < 0 || F < 0 || S < 1 || D > FS_MAX_D) return FCN_E_BADARG;
+    if (!fs_sizes_ok(F, pt_stride, D, S)) return FCN_E_BADARG;
     if (D == 0 || F == 0) return 0;
     if (!frame_pts || !frame_off || !K || !Rtilt || !boxes || !box_frame || !seg_off || !out_pts) return FCN_E_BADARG;
     SrArgs a;
-    sr_args(a, frame_pts, frame_off, F, pt_stride, K, Rtilt, boxes, box_frame, D, S);
-    a.soff = seg_off; a.out = out_pts;
-    return sr_launch(a, true, false, (hipStream_t)stream);
+    sr_args(a, frame_pts, frame_off, F, pt_stride, K, Rtilt, boxes, box_frame, S);
+    a.c.soff = seg_off; a.c.out = out_pts;
+    return sr_launch<false, true>(a, D, (hipStream_t)stream, true);
 }
 
 // What the labelled entries below and the no-read pair of frustum_sunrgbd_plan.h (fcn_frustum_sunrgbd_train_count / _fill) share:
@@ -294,20 +188,16 @@ static inline int sr_label_count_launch(const float *frame_pts, const int64_t *f
                                         const double *gt_box3d, double *frustum_angle, int32_t *seg_cnt, int32_t *seg_pos,
                                         double *corners, void *stream, bool read_lists)
 {
-    if (pt_stride < 3 || D < 0 || F < 0 || S < 1 || D > FS_MAX_D) return FCN_E_BADARG;
+    if (!fs_sizes_ok(F, pt_stride, D, S)) return FCN_E_BADARG;
     if (D == 0) return 0;
     if (!seg_cnt || !seg_pos) return FCN_E_BADARG;
-    if (F == 0) {
-        hipError_t e = hipMemsetAsync(seg_cnt, 0, (size_t)D * S * sizeof(int32_t), (hipStream_t)stream);
-        if (e == hipSuccess) e = hipMemsetAsync(seg_pos, 0, (size_t)D * S * sizeof(int32_t), (hipStream_t)stream);
-        return (int)e;
-    }
+    if (F == 0) return sc_zero_counts(seg_cnt, seg_pos, (size_t)D * S, (hipStream_t)stream);
     if (!frame_pts || !frame_off || !K || !Rtilt || !boxes || !box_frame || !gt_box3d || !frustum_angle || !corners)
         return FCN_E_BADARG;
     SrArgs a;
-    sr_args(a, frame_pts, frame_off, F, pt_stride, K, Rtilt, boxes, box_frame, D, S);
-    a.gt = gt_box3d; a.angle = frustum_angle; a.scnt = seg_cnt; a.spos = seg_pos; a.corners = corners;
-    return sr_launch(a, false, true, (hipStream_t)stream, read_lists);
+    sr_args(a, frame_pts, frame_off, F, pt_stride, K, Rtilt, boxes, box_frame, S);
+    a.gt = gt_box3d; a.angle = frustum_angle; a.c.scnt = seg_cnt; a.c.spos = seg_pos; a.corners = corners;
+    return sr_launch<true, false>(a, D, (hipStream_t)stream, read_lists);
 }
 
 static inline int sr_label_fill_launch(const float *frame_pts, const int64_t *frame_off, int F, int pt_stride, const double *K,
@@ -315,14 +205,14 @@ static inline int sr_label_fill_launch(const float *frame_pts, const int64_t *fr
                                        const double *gt_box3d, const int64_t *seg_off, float *out_pts, int64_t *out_seg,
                                        void *stream, bool read_lists)
 {
-    if (pt_stride < 3 || D < 0 || F < 0 || S < 1 || D > FS_MAX_D) return FCN_E_BADARG;
+    if (!fs_sizes_ok(F, pt_stride, D, S)) return FCN_E_BADARG;
     if (D == 0 || F == 0) return 0;
     if (!frame_pts || !frame_off || !K || !Rtilt || !boxes || !box_frame || !gt_box3d || !seg_off || !out_pts || !out_seg)
         return FCN_E_BADARG;
     SrArgs a;
-    sr_args(a, frame_pts, frame_off, F, pt_stride, K, Rtilt, boxes, box_frame, D, S);
-    a.gt = gt_box3d; a.soff = seg_off; a.out = out_pts; a.oseg = out_seg;
-    return sr_launch(a, true, true, (hipStream_t)stream, read_lists);
+    sr_args(a, frame_pts, frame_off, F, pt_stride, K, Rtilt, boxes, box_frame, S);
+    a.gt = gt_box3d; a.c.soff = seg_off; a.c.out = out_pts; a.c.oseg = out_seg;
+    return sr_launch<true, true>(a, D, (hipStream_t)stream, read_lists);
 }
 
 extern "C" int fcn_frustum_sunrgbd_label_count(const float *frame_pts, const int64_t *frame_off, int F, int pt_stride,

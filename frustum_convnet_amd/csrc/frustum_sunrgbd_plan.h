@@ -5,8 +5,8 @@
 // input" states the contract bit for bit; tests/sunrgbd_plan_ref.py restates it in numpy):
 //   fcn_box2d_perturb_sunrgbd        sunrgbd/sunrgbd_utils.py::random_shift_box2d (:208-221) for D boxes, one lane per box, on tag 3 of
 //                                    the draws' counter layout (fcn_box2d_perturb's stream): no clip, no retry, nothing can fail;
-//   fcn_frustum_sunrgbd_train_count  sr_count_kernel / sr_fill_kernel of frustum_sunrgbd.h as they are, launched without
-//   fcn_frustum_sunrgbd_train_fill   fs_read_lists: the kernels skip a box whose frame is out of range; "no frame longer than
+//   fcn_frustum_sunrgbd_train_count  the labelled count / fill of frustum_sunrgbd.h (seg_compact.h with SrSelect<true>), launched without
+//   fcn_frustum_sunrgbd_train_fill   a read-back: the kernels skip a box whose frame is out of range; "no frame longer than
 //                                    S * FS_SEG rows" is the caller's duty (checked once, where the frames are made resident);
 //   fcn_frustum_sunrgbd_train_plan   ONE workgroup between the two: the full-positive bar per box (pre-kept), the exclusive prefix sum
 //                                    of the pre-kept boxes' segment counts (int64, clamped to the capacity of the point buffer), the

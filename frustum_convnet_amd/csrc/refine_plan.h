@@ -3,8 +3,8 @@
 // look-ups of RefineInputBuilder.build_device_train do per step, as launches that read nothing back -- a fixed batch of B slots at
 // fixed window counts, capturable into a hipGraph (INTEGRATION.md "Capturable refine-stage training input" states the contract bit
 // for bit; tests/refine_plan_ref.py restates it in numpy):
-//   fcn_refine_train_match     rl_match_kernel / rl_count_kernel / rl_fill_kernel of refine_label.h as they are, launched without
-//   fcn_refine_train_count     rs_candidates_in_range and rl_read_lists: the kernels skip a candidate whose row, frame or label is
+//   fcn_refine_train_match     rl_match_kernel and the count / fill of refine_label.h (seg_compact.h with RlSelect), launched without
+//   fcn_refine_train_count     a read-back of the index lists: the kernels skip a candidate whose row, frame or label is
 //   fcn_refine_train_fill      out of range (it is no longer REPORTED); "no frame longer than S * FS_SEG rows" is the caller's duty
 //                              (checked once, where the frames are made resident);
 //   fcn_box3d_jitter_draw      the (D, A, 7) uniforms rl_jitter reads, one lane per unit, on the counter-based stream of draws.h

@@ -40,28 +40,40 @@ def _calib(calib, img_size, F, dev):
     return out + [wh.view(F, 2)]
 
 
-def _setup(who, frame_points, frame_off, calib, img_size, boxes2d, box_frame, clip_distance, clip_boxes):
-    """The arguments both pairs of entry points share (fs_in of _native.py) from the Python-level inputs, the tensors that back
-    them, and F, ps, D, S."""
+def _frames(who, frame_points, frame_off, resident=False):
+    """What every entry point of the input side takes its frames as: the points as contiguous float32 (n, >= 3) on the device (one
+    placeholder row when the buffer is empty), frame_off on the device as int64, and F, ps, S -- S the longest frame in segments
+    of fcn_frustum_select_seg() rows, from the F + 1 offsets on the host.  resident (the *TrainSource classes, which check the
+    frames HERE, once, and launch without a read-back): refuse offsets that are not ascending within the buffer."""
     _need_cuda(frame_points, who)
     dev = frame_points.device
     pts = frame_points.detach().contiguous().float()
     if pts.dim() != 2 or pts.shape[1] < 3:
         raise ValueError("%s: frame_points must be (n, >= 3), got %s" % (who, tuple(frame_points.shape)))
     foff_h = torch.as_tensor(frame_off).detach().cpu().to(torch.int64).contiguous().view(-1)      # F + 1 integers: they decide S
-    foff = foff_h.to(dev, non_blocking=True)
     F, ps = int(foff_h.numel()) - 1, int(pts.shape[1])
+    lengths = foff_h[1:] - foff_h[:-1]
+    if resident and (F < 1 or int(foff_h[0]) < 0 or bool((lengths < 0).any()) or int(foff_h[-1]) > pts.shape[0]):
+        raise ValueError("%s: frame_off must be F + 1 >= 2 ascending row offsets into the %d rows" % (who, pts.shape[0]))
+    foff = foff_h.to(dev, non_blocking=True)
+    seg = int(_native.lib().fcn_frustum_select_seg())
+    S = max(1, -(-(int(lengths.max()) if F > 0 else 0) // seg))
+    if pts.shape[0] == 0:
+        pts = torch.zeros((1, ps), dtype=torch.float32, device=dev)        # (an address to hand in: every frame is empty)
+    return pts, foff, F, ps, S
+
+
+def _setup(who, frame_points, frame_off, calib, img_size, boxes2d, box_frame, clip_distance, clip_boxes):
+    """The arguments both pairs of entry points share (fs_in of _native.py) from the Python-level inputs, the tensors that back
+    them, and F, ps, D, S."""
+    pts, foff, F, ps, S = _frames(who, frame_points, frame_off)
+    dev = frame_points.device
     P, V2C, R0, wh = _calib(calib, img_size, F, dev)
     boxes = torch.as_tensor(boxes2d).to(device=dev, dtype=torch.float64).contiguous().view(-1, 4)
     bframe = torch.as_tensor(box_frame).to(device=dev, dtype=torch.int32).contiguous().view(-1)
     D = int(bframe.numel())
     if boxes.shape[0] != D:
         raise ValueError("%s: %d boxes but %d frames" % (who, boxes.shape[0], D))
-    seg = int(_native.lib().fcn_frustum_select_seg())
-    longest = int((foff_h[1:] - foff_h[:-1]).max()) if F > 0 else 0
-    S = max(1, -(-longest // seg))
-    if pts.shape[0] == 0:
-        pts = torch.zeros((1, ps), dtype=torch.float32, device=dev)        # (an address to hand in: every frame is empty)
     args = (pts.data_ptr(), foff.data_ptr(), F, ps, P.data_ptr(), V2C.data_ptr(), R0.data_ptr(), wh.data_ptr(), boxes.data_ptr(),
             bframe.data_ptr(), D, S, 1 if clip_boxes else 0, float(clip_distance))
     return args, (pts, foff, P, V2C, R0, wh, boxes, bframe), ps, D, S
@@ -262,14 +274,8 @@ def subsampled_counts(counts, sub):
 
 def _setup_sunrgbd(who, frame_points, frame_off, K, Rtilt, boxes2d, box_frame):
     """The arguments the four entry points share (sr_in of _native.py), the tensors that back them, and ps, D, S."""
-    _need_cuda(frame_points, who)
+    pts, foff, F, ps, S = _frames(who, frame_points, frame_off)
     dev = frame_points.device
-    pts = frame_points.detach().contiguous().float()
-    if pts.dim() != 2 or pts.shape[1] < 3:
-        raise ValueError("%s: frame_points must be (n, >= 3), got %s" % (who, tuple(frame_points.shape)))
-    foff_h = torch.as_tensor(frame_off).detach().cpu().to(torch.int64).contiguous().view(-1)      # F + 1 integers: they decide S
-    foff = foff_h.to(dev, non_blocking=True)
-    F, ps = int(foff_h.numel()) - 1, int(pts.shape[1])
     cal = []
     for name, m in (("K", K), ("Rtilt", Rtilt)):
         t = torch.as_tensor(m).to(device=dev, dtype=torch.float64).contiguous()
@@ -281,11 +287,6 @@ def _setup_sunrgbd(who, frame_points, frame_off, K, Rtilt, boxes2d, box_frame):
     D = int(bframe.numel())
     if boxes.shape[0] != D:
         raise ValueError("%s: %d boxes but %d frames" % (who, boxes.shape[0], D))
-    seg = int(_native.lib().fcn_frustum_select_seg())
-    longest = int((foff_h[1:] - foff_h[:-1]).max()) if F > 0 else 0
-    S = max(1, -(-longest // seg))
-    if pts.shape[0] == 0:
-        pts = torch.zeros((1, ps), dtype=torch.float32, device=dev)        # (an address to hand in: every frame is empty)
     args = (pts.data_ptr(), foff.data_ptr(), F, ps, cal[0].data_ptr(), cal[1].data_ptr(), boxes.data_ptr(), bframe.data_ptr(), D, S)
     return args, (pts, foff, cal[0], cal[1], boxes, bframe), ps, D, S
 
@@ -428,20 +429,9 @@ class FrameTrainSource:
                  seed, perturb=True, pick=True, shift_ratio=0.1, min_box_height=25.0, clip_distance=2.0, select_box2d=None):
         from .inputs import DeviceDraws
         who = "FrameTrainSource"
-        _need_cuda(frame_points, who)
+        pts, foff, F, ps, S = _frames(who, frame_points, frame_off, resident=True)
         dev = frame_points.device
         L = _native.lib()
-        pts = frame_points.detach().contiguous().float()
-        if pts.dim() != 2 or pts.shape[1] < 3:
-            raise ValueError("%s: frame_points must be (n, >= 3), got %s" % (who, tuple(frame_points.shape)))
-        foff_h = torch.as_tensor(frame_off).detach().cpu().to(torch.int64).contiguous().view(-1).numpy()
-        F, ps = len(foff_h) - 1, int(pts.shape[1])
-        if F < 1 or foff_h[0] < 0 or (np.diff(foff_h) < 0).any() or foff_h[-1] > pts.shape[0]:
-            raise ValueError("%s: frame_off must be F + 1 >= 2 ascending row offsets into the %d rows" % (who, pts.shape[0]))
-        seg = int(L.fcn_frustum_select_seg())
-        S = max(1, -(-int(np.diff(foff_h).max()) // seg))       # no frame is longer than S segments: checked HERE, once
-        if pts.shape[0] == 0:
-            pts = torch.zeros((1, ps), dtype=torch.float32, device=dev)
         P, V2C, R0, wh = _calib(calib, img_size, F, dev)
         host = lambda a: (a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a))
         gt2d = np.ascontiguousarray(host(gt_box2d), dtype=np.float64).reshape(-1, 4)
@@ -496,7 +486,7 @@ class FrameTrainSource:
         f64, i32, i64 = (dict(dtype=t, device=dev) for t in (torch.float64, torch.int32, torch.int64))
         N = builder.npoints
         # ---- resident: the frames, the per-label tensors
-        self.frames = (pts, up(foff_h), P, V2C, R0, wh)
+        self.frames = (pts, foff, P, V2C, R0, wh)
         self.g_box2d, self.g_sel2d, self.g_box3d, self.g_frame = up(gt2d), up(sel2d), up(gt3d), up(bf.astype(np.int32))
         self.g_heading, self.g_size = self.g_box3d[:, 6].contiguous(), self.g_box3d[:, 3:6].contiguous()
         self.g_P = P.index_select(0, self.g_frame.to(torch.int64)).contiguous()
@@ -628,20 +618,9 @@ class SunrgbdTrainSource:
                  perturb=True, pick=True, shift_ratio=0.1, cap=SUNRGBD_CAP, min_positives=SUNRGBD_MIN, select_box2d=None, sub=None):
         from .inputs import DeviceDraws
         who = "SunrgbdTrainSource"
-        _need_cuda(frame_points, who)
+        pts, foff, F, ps, S = _frames(who, frame_points, frame_off, resident=True)
         dev = frame_points.device
         L = _native.lib()
-        pts = frame_points.detach().contiguous().float()
-        if pts.dim() != 2 or pts.shape[1] < 3:
-            raise ValueError("%s: frame_points must be (n, >= 3), got %s" % (who, tuple(frame_points.shape)))
-        foff_h = torch.as_tensor(frame_off).detach().cpu().to(torch.int64).contiguous().view(-1).numpy()
-        F, ps = len(foff_h) - 1, int(pts.shape[1])
-        if F < 1 or foff_h[0] < 0 or (np.diff(foff_h) < 0).any() or foff_h[-1] > pts.shape[0]:
-            raise ValueError("%s: frame_off must be F + 1 >= 2 ascending row offsets into the %d rows" % (who, pts.shape[0]))
-        seg = int(L.fcn_frustum_select_seg())
-        S = max(1, -(-int(np.diff(foff_h).max()) // seg))       # no frame is longer than S segments: checked HERE, once
-        if pts.shape[0] == 0:
-            pts = torch.zeros((1, ps), dtype=torch.float32, device=dev)
         cal = []
         for name, m in (("K", K), ("Rtilt", Rtilt)):
             t = torch.as_tensor(m).to(device=dev, dtype=torch.float64).contiguous()
@@ -690,7 +669,7 @@ class SunrgbdTrainSource:
         f64, i32, i64 = (dict(dtype=t, device=dev) for t in (torch.float64, torch.int32, torch.int64))
         N = builder.npoints
         # ---- resident: the frames, the per-label tensors
-        self.frames = (pts, up(foff_h), cal[0], cal[1])
+        self.frames = (pts, foff, cal[0], cal[1])
         self.g_box2d, self.g_sel2d, self.g_box3d, self.g_frame = up(gt2d), up(sel2d), up(gt3d), up(bf.astype(np.int32))
         self.g_heading = self.g_box3d[:, 6].contiguous()
         self.g_size = (self.g_box3d[:, 3:6] * 2.0).contiguous()                 # box3d_size = 2l, 2w, 2h

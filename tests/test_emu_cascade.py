@@ -21,6 +21,9 @@ CASES = [
     ("test_out_of_range_candidate_is_reported_and_never_dereferenced", ("row_high",)),
     ("test_out_of_range_candidate_is_reported_and_never_dereferenced", ("row_negative",)),
     ("test_fill_never_writes_past_a_candidates_slice", ()),
+    ("test_select_over_the_frame_lengths_the_scan_turns_on", (3,)),
+    ("test_select_over_the_frame_lengths_the_scan_turns_on", (4,)),
+    ("test_select_over_the_frame_lengths_the_scan_turns_on", (5,)),
     ("test_build_device_equals_build_on_host_records", ()),
     ("test_two_stage_detector_equals_the_hand_composed_sequence", ()),
 ]

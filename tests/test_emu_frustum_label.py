@@ -15,6 +15,7 @@ CASES = [
     ("test_label_entry_points_match_the_referee", (3,)),
     ("test_label_entry_points_match_the_referee", (4,)),
     ("test_label_entry_points_match_the_referee", (5,)),
+    ("test_label_rows_that_are_not_16_byte_aligned", ()),
     ("test_points_exactly_on_a_face_are_inside_and_one_step_out_is_outside", ()),
     ("test_slices_bound_both_stores", ()),
     ("test_label_bad_arguments_are_refused_with_nothing_written", ()),

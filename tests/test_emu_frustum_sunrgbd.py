@@ -14,6 +14,7 @@ pytestmark = pytest.mark.skipif(not (os.path.exists(CLANG) or shutil.which(CLANG
 
 CASES = [
     ("test_entry_points_match_the_referee", (3,)),
+    ("test_entry_points_match_the_referee", (5,)),
     ("test_entry_points_match_the_referee", (6,)),
     ("test_entry_points_match_the_referee", (7,)),
     ("test_entry_points_match_the_referee", (4,)),

@@ -16,6 +16,9 @@ CASES = [
     ("test_entry_points_match_the_referee", (4,)),
     ("test_entry_points_match_the_referee", (5,)),
     ("test_entry_points_match_the_referee", ("unaligned4",)),
+    ("test_count_and_fill_over_the_frame_lengths_the_scan_turns_on", (3,)),
+    ("test_count_and_fill_over_the_frame_lengths_the_scan_turns_on", (4,)),
+    ("test_count_and_fill_over_the_frame_lengths_the_scan_turns_on", (5,)),
     ("test_one_copy_without_jitter_equals_the_unlabelled_selection", ()),
     ("test_copies_chain_as_the_references_do", ()),
     ("test_points_exactly_on_a_face_are_inside_and_one_step_out_is_outside", ()),

@@ -243,6 +243,55 @@ def test_fill_never_writes_past_a_candidates_slice():
         assert np.array_equal(_bits(rows[ooff[d]:ooff[d + 1]]), _bits(exp)), d
 
 
+@functools.lru_cache(maxsize=None)
+def _edge_scene(stride):
+    """The frame lengths the shared scan-and-compact skeleton's paths turn on (csrc/seg_compact.h; seg = fcn_frustum_select_seg()),
+    one frame each, and one candidate per frame that holds most of it.  The link scans a whole frame as ONE segment: these are
+    its empty, partial, one-iteration and many-iteration quarters."""
+    from frustum_convnet_amd import _native
+    seg = int(_native.lib().fcn_frustum_select_seg())
+    lengths = (0, 1, 63, 64, 65, 255, seg - 1, seg, seg + 1, 2 * seg + 100)
+    rng = np.random.RandomState(177 + stride)
+    n = sum(lengths)
+    pts = np.zeros((n, stride), dtype=np.float32)
+    pts[:, 0], pts[:, 1], pts[:, 2] = rng.uniform(-8, 8, n), rng.uniform(0, 2, n), rng.uniform(5, 25, n)
+    pts[:, 3:] = rng.uniform(0, 1, (n, stride - 3))
+    off = np.concatenate([[0], np.cumsum(lengths)]).astype(np.int64)
+    dets = np.tile(np.asarray([0.0, 1.0 + 1.5, 15.0, 12.0, 14.0, 3.0, 2.5, 0.5], dtype=np.float32), (len(lengths), 1))
+    dets[:, 6] += np.linspace(0.0, 0.5, len(lengths)).astype(np.float32)         # (a box of its own per frame)
+    crow = cframe = np.arange(len(lengths), dtype=np.int32)
+    ref = cascade_ref.select(pts, off, dets, crow, cframe, 1.2)
+    c = ref["counts"]
+    assert c[0] == 0 and (c[2:] > 0).all() and (c[2:] < np.asarray(lengths[2:])).all() and (c[6:] % 64 != 0).any()
+    return {"pts": pts, "off": off, "dets": dets, "crow": crow, "cframe": cframe, "ref": ref}
+
+
+@pytest.mark.parametrize("stride", [3, 4, 5])
+def test_select_over_the_frame_lengths_the_scan_turns_on(stride):
+    """Frames of 0, 1, 63, 64, 65, 255, seg - 1, seg, seg + 1 and 2 * seg + 100 rows at strides 3, 4 and 5: counts and rows equal the
+    referee's, bit for bit and in order; at stride 4 a buffer that starts 4 bytes into an allocation (the scalar path) gives the
+    rows of the aligned run; offsets that grant nothing store nothing."""
+    sc = _edge_scene(stride)
+    ref = sc["ref"]
+    t = _tensors(sc)
+    rc, o = _count(t)
+    assert rc == 0 and np.array_equal(o["cnt"].cpu().numpy(), ref["counts"])
+    rc, rows, guard, _ = _fill(t, ref["counts"])
+    assert rc == 0 and (guard == -7.0).all()
+    assert np.array_equal(_bits(rows), _bits(_expected_rows(sc)))
+    if stride == 4:
+        flat = torch.zeros(sc["pts"].size + 1, dtype=torch.float32, device="cuda")
+        flat[1:] = t["pts"].reshape(-1)
+        tu = dict(t, pts=flat[1:].view(-1, 4))
+        assert tu["pts"].data_ptr() % 16 == 4
+        rc, ou = _count(tu)
+        assert rc == 0 and torch.equal(ou["cnt"].cpu(), o["cnt"].cpu())
+        rc, rows_u, guard, _ = _fill(tu, ref["counts"])
+        assert rc == 0 and np.array_equal(_bits(rows_u), _bits(rows)) and (guard == -7.0).all()
+    rc, rows, guard, _ = _fill(t, np.zeros_like(ref["counts"]))          # the empty grant
+    assert rc == 0 and rows.shape == (0, stride) and (guard == -7.0).all()
+
+
 def _builder(npoints):
     from frustum_convnet_amd import inputs
     from frustum_convnet_amd.config import reset_cfg

@@ -347,6 +347,9 @@ def test_fill_never_writes_past_a_slice():
             i = dd * S + ss
             sel = ref["rows"][dd][(ref["index"][dd] // seg) == ss][:counts[dd, ss]]
             _check_rows(rows[soff[i]:soff[i + 1]], sel, "")
+    # every box granted nothing: nothing is written at all
+    rc, rows, guard, _ = _fill(t, S, np.zeros_like(counts))
+    assert rc == 0 and len(rows) == 0 and (guard == -7.0).all()
 
 
 def _cal(t):

@@ -191,6 +191,26 @@ def test_label_entry_points_match_the_referee(stride):
     assert np.array_equal(o5["scnt"].cpu().numpy()[:, :S], ref["seg_cnt"]) and (o5["scnt"].cpu().numpy()[:, S:] == 0).all()
 
 
+def test_label_rows_that_are_not_16_byte_aligned():
+    """pt_stride 4 takes 16-byte accesses only when the buffers allow it: a view that starts 4 bytes into an allocation must give
+    the aligned run's counts, positives, rows and labels through the word-by-word path, bit for bit."""
+    sc = _scene(4)
+    S = sc["S"]
+    t = _tensors(sc)
+    rc, o = _count(t, S)
+    rc_f, rows_a, seg_a, _, _ = _fill(t, S, o["scnt"].cpu().numpy())
+    assert rc == 0 and rc_f == 0 and np.array_equal(o["scnt"].cpu().numpy(), sc["ref"]["seg_cnt"])
+    flat = torch.zeros(sc["pts"].size + 1, dtype=torch.float32, device="cuda")
+    flat[1:] = t["pts"].reshape(-1)
+    t["pts"] = flat[1:].view(-1, 4)
+    assert t["pts"].data_ptr() % 16 == 4
+    rc, o2 = _count(t, S)
+    assert rc == 0 and all(torch.equal(o2[k], o[k]) for k in o)
+    rc, rows, seg, guard, _ = _fill(t, S, o2["scnt"].cpu().numpy())
+    assert rc == 0 and _guards_intact(guard)
+    assert np.array_equal(_bits(rows), _bits(rows_a)) and np.array_equal(seg, seg_a)
+
+
 def test_points_exactly_on_a_face_are_inside_and_one_step_out_is_outside():
     """An axis-aligned box (ry = 0) with dyadic centre and sizes, identity V2C / R0 and a plain pinhole P: the float32 rect row IS
     the input row.  Per face: one float32 step inside, exactly on it, one step outside -> 1, 1, 0."""

@@ -32,7 +32,7 @@ WHOLE_2D = [-60.0, -60.0, 800.0, 600.0]
 INNER_2D = [150.25, 100.5, 450.75, 400.0]
 # the kernels load a row in one 16-byte piece (stride 4, 16-byte aligned) or word by word; "4+4", "4+8", "6+4": that stride in a
 # buffer that starts 4 / 8 bytes behind a 16-byte boundary (word by word)
-STRIDES = [3, 6, 7, 4, "4+4", "4+8", "6+4"]
+STRIDES = [3, 5, 6, 7, 4, "4+4", "4+8", "6+4"]
 
 
 @functools.lru_cache(maxsize=None)

@@ -184,6 +184,39 @@ def test_entry_points_match_the_referee(stride):
     assert np.array_equal(o5["spos"][:, :S], ref["seg_pos"]) and (o5["spos"][:, S:] == 0).all()
 
 
+@pytest.mark.parametrize("stride", [3, 4, 5])
+def test_count_and_fill_over_the_frame_lengths_the_scan_turns_on(stride):
+    """The cascade link's edge scene (frames of 0, 1, 63, 64, 65, 255, seg - 1, seg, seg + 1, 2 * seg + 100 rows, one candidate per
+    frame) with every candidate's own row as its label box, one un-jittered copy: per-segment counts and positives equal the
+    referee's, rows bit for bit and in order; at stride 4 a buffer that starts 4 bytes into an allocation (the word-by-word path)
+    gives the aligned run's answer; offsets that grant nothing store nothing."""
+    from test_gpu_cascade import _edge_scene
+    es = _edge_scene(stride)
+    D, S = len(es["crow"]), 3
+    cgt, gt = np.arange(D, dtype=np.int32), es["dets"][:, :7].astype(np.float64)
+    ref = rr.select_labeled(es["pts"], es["off"], es["dets"], es["crow"], es["cframe"], cgt, gt, None)
+    want_cnt = _seg_counts(ref["index"], S)
+    want_pos = _seg_counts([ix[p] for ix, p in zip(ref["index"], ref["positive"])], S)
+    assert (want_cnt[-1] > 0).all() and 0 < want_pos.sum() < want_cnt.sum()
+    want = np.concatenate([es["pts"][int(es["off"][f]):][ix] for f, ix in enumerate(ref["index"])], 0)
+    t = {k: _dev(v) for k, v in dict(es, cgt=cgt, gt=gt).items() if k != "ref"}
+    rc, o = _count(t, S, jitter=False)
+    assert rc == 0 and np.array_equal(o["scnt"], want_cnt) and np.array_equal(o["spos"], want_pos)
+    rc, buf, _ = _fill(t, S, o["scnt"], jitter=False)
+    assert rc == 0 and np.array_equal(_bits(buf[:len(want)]), _bits(want)) and (buf[len(want):] == -7.0).all()
+    if stride == 4:
+        flat = torch.zeros(es["pts"].size + 1, dtype=torch.float32, device="cuda")
+        flat[1:] = t["pts"].reshape(-1)
+        tu = dict(t, pts=flat[1:].view(-1, 4))
+        assert tu["pts"].data_ptr() % 16 == 4
+        rc, ou = _count(tu, S, jitter=False)
+        assert rc == 0 and all(np.array_equal(ou[k], o[k]) for k in o)
+        rc, buf_u, _ = _fill(tu, S, ou["scnt"], jitter=False)
+        assert rc == 0 and np.array_equal(_bits(buf_u), _bits(buf))
+    rc, buf, _ = _fill(t, S, np.zeros_like(want_cnt), jitter=False)      # the empty grant
+    assert rc == 0 and (buf == -7.0).all()
+
+
 def test_one_copy_without_jitter_equals_the_unlabelled_selection():
     """A = 1 and jitter = NULL on the fixture's candidates against fcn_refine_select_count / _fill on the same candidates:
     counts, rows and pred_* bit-identical.  Every candidate is given a label row, so every unit selects."""
