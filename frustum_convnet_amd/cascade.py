@@ -7,7 +7,9 @@ on the host -- once per box over the frame's whole point cloud -- and pickles th
 Here the selection is two HIP launches and the selected points go straight into RefineInputBuilder.build_device; between the
 stages the host reads the first stage's keep lists, D point counts and D predicted widths, and each of the two entry points
 reads the 2 * D candidate indices back to range-check them (five small reads that wait for the stream; no point data).  No CPU
-fallback.
+fallback.  CascadeLink (TwoStageDetector.link) is the same link as ONE capturable sequence of launches at a fixed number of
+candidates, a fixed batch size and fixed window counts, with no host read (C-ABI fcn_cascade_candidates, fcn_refine_detect_count /
+_plan / _fill, csrc/cascade_plan.h).
 
 Training the refinement stage on the first stage's output (extract_frustum_det_data :406-592: match to the labels, enlarge, jitter,
 select, count the positives, reject) is match_detections + draw_box3d_jitter + refine_training_candidates (C-ABI fcn_refine_match,
@@ -188,7 +190,10 @@ STATUS_BITS = ((1, "bit 0: a slot had no row to draw from (its choice row is zer
                (2, "bit 1: fewer units survived than the batch has slots (the empty slots hold the spare unit box over no rows)"),
                (4, "bit 2: the selected rows exceed the capacity of the point buffer (the overflow was dropped)"),
                (32, "bit 5: a unit's predicted width needs more windows than lpad on some stride (the unit was dropped)"),
-               (64, "bit 6: a unit's predicted width is not a positive finite number (the unit was dropped)"))
+               (64, "bit 6: a unit's predicted width is not a positive finite number (the unit was dropped)"),
+               (128, "bit 7: the first stage kept more rows than the link has candidates (the rest were dropped)"),
+               (256, "bit 8: more candidates survived than the batch has slots (the rest were dropped)"),
+               (512, "bit 9: a first-stage group overflowed the NMS (cnt = -1) or reports cnt > top_k (it was passed on to nobody)"))
 
 
 class RefineTrainSource:
@@ -394,6 +399,182 @@ class RefineTrainSource:
             raise ValueError("RefineTrainSource: status %d -- %s" % (s, "; ".join(text for bit, text in STATUS_BITS if s & bit)))
 
 
+# ------------------------------------------------------------------------------------------------
+# Two-stage inference as ONE capturable sequence of launches (csrc/cascade_plan.h)
+class CascadeLink:
+    """A first-stage batch -> second-stage detections at a FIXED number of candidates D, a FIXED second-stage batch size B and
+    FIXED window counts lpad, with no host read, no upload and no validation per step: what TwoStageDetector.detect does behind its
+    five synchronisations, as one sequence of launches that can be captured into a hipGraph and replayed on new first-stage batches
+    written into the same tensors (INTEGRATION.md "Capturable two-stage inference" states the contract).
+    stage1, stage2: two PointNetDet models in eval mode; refine_builder: the second stage's RefineInputBuilder; frame_points: a
+    contiguous (n, >= 3) float32 device tensor, HELD, not copied -- a caller may overwrite it in place between replays -- and
+    frame_off (F+1) as refine_candidates takes it (copied to the device as .frame_off; S, the segments of the longest frame, is
+    fixed here: frames written later must not be longer than S * fcn_frustum_select_seg() rows); B1 / L2: frustums and windows of
+    the first-stage batch step() takes; G: the (frame, class) groups of the first stage; top_k, method, thresh: as PointNetDet.detect,
+    for both stages; D: candidates per step (kept rows beyond D are dropped and flagged); B: slots of the second-stage batch (B <= D;
+    survivors beyond B are dropped and flagged); capacity: rows of the point buffer (rows beyond it are dropped and flagged); lpad:
+    four ints, the padded window counts of center_ref1..4 (a candidate whose predicted width needs more is dropped and flagged);
+    seed: keys the DeviceDraws of the per-sample resample, one step further after every step().
+    unit_frame, unit_class (index into refine_builder.classes), unit_group (B1) int32 device tensors describe the frustums of the
+    first-stage batch: zeros at first -- fill them with set_units() or overwrite them in place between replays.
+    Everything is validated here, once, on the host; step() validates nothing and reads nothing."""
+
+    def __init__(self, stage1, stage2, refine_builder, frame_points, frame_off, B1, L2, G, top_k, D, B, capacity, lpad, seed, method,
+                 thresh, ratio=1.2):
+        from .inputs import DeviceDraws
+        who = "CascadeLink"
+        if not (isinstance(frame_points, torch.Tensor) and frame_points.is_cuda and frame_points.dtype == torch.float32 and
+                frame_points.is_contiguous() and frame_points.dim() == 2 and frame_points.shape[0] >= 1 and not frame_points.requires_grad):
+            raise ValueError("%s: frame_points must be a contiguous (n >= 1, >= 3) float32 device tensor (it is held, not copied)" % who)
+        pts, foff, F, ps, S = _frames(who, frame_points, frame_off, resident=True)
+        dev = frame_points.device
+        if stage1.training or stage2.training:
+            raise ValueError("%s: both models must be in eval mode" % who)
+        builder = refine_builder
+        if builder.device.type != "cuda":
+            raise RuntimeError("frustum_convnet_amd: input construction is a HIP kernel (MI355X only); no CPU fallback")
+        B1, L2, G, top_k, D, B, capacity = (int(x) for x in (B1, L2, G, top_k, D, B, capacity))
+        max_u, max_segs = RefineTrainSource.limits()
+        if B1 < 1 or L2 < 1 or G < 1 or G > 65536:
+            raise ValueError("%s: need B1 >= 1, L2 >= 1 and 1 <= G <= 65536, got B1 = %d, L2 = %d, G = %d" % (who, B1, L2, G))
+        if not (1 <= top_k <= 4096):
+            raise ValueError("%s: top_k must lie in [1, 4096] (the NMS sorts at most 4096 rows of a group), got %d" % (who, top_k))
+        if not (1 <= B <= D <= max_u):
+            raise ValueError("%s: need 1 <= B <= D <= %d, got B = %d, D = %d" % (who, max_u, B, D))
+        if D * S > max_segs:
+            raise ValueError("%s: D * S = %d * %d segments exceed the plan's %d" % (who, D, S, max_segs))
+        if capacity < 1:
+            raise ValueError("%s: capacity must be >= 1 row, got %d" % (who, capacity))
+        lpad = [int(x) for x in lpad]
+        if len(lpad) != 4 or min(lpad) < 1:
+            raise ValueError("%s: lpad must be four window counts >= 1, got %r" % (who, lpad))
+        if any(lpad[s + 1] != (lpad[s] + 1) // 2 for s in range(3)):       # (what RefineInputBuilder._lpad gives for any width)
+            raise ValueError("%s: the second stage halves the windows level by level: lpad[s + 1] must be ceil(lpad[s] / 2), got %r" %
+                             (who, lpad))
+        if method not in ("nms", "top"):
+            raise ValueError("%s: method must be 'nms' or 'top', got %r" % (who, method))
+        if not (float(ratio) > 0.0) or not np.isfinite(float(thresh)):
+            raise ValueError("%s: ratio must be positive and thresh finite, got %r, %r" % (who, ratio, thresh))
+        self.device, self.stage1, self.stage2, self.builder, self.lpad = dev, stage1, stage2, builder, lpad
+        self.B1, self.L2, self.G, self.top_k, self.D, self.B, self.F, self.S, self.ps = B1, L2, G, top_k, D, B, F, S, ps
+        self.R, self.capacity, self.method, self.thresh, self.ratio = B1 * L2, capacity, method, float(thresh), float(ratio)
+        f32, f64, i32, i64 = (dict(dtype=t, device=dev) for t in (torch.float32, torch.float64, torch.int32, torch.int64))
+        N, C = builder.npoints, len(builder.classes)
+        # ---- resident: the frames (held) and the frustums' tables
+        self.frames, self.frame_off = (pts, foff), foff
+        self.unit_frame, self.unit_class, self.unit_group = (torch.zeros((B1,), **i32) for _ in range(3))
+        self.eye = torch.eye(C, **f32)
+        self.strides_c = (ctypes.c_double * 4)(*builder.strides)
+        self.lpad_c = (ctypes.c_int32 * 4)(*lpad)
+        self.draws = DeviceDraws(int(seed), builder.device)
+        self.status = torch.zeros((1,), **i32)
+        # ---- every intermediate.  The per-candidate tables have D + 1 rows: row D is the spare entry an empty slot gathers -- no
+        # first-stage row, class 0, the spare group G, score 0, a unit box at the origin -- written here once and never by a kernel
+        self.cand_row, self.cand_frame = torch.full((D + 1,), -1, **i32), torch.full((D + 1,), -1, **i32)
+        self.cand_class, self.cand_group = torch.zeros((D + 1,), **i32), torch.full((D + 1,), G, **i32)
+        self.cand_score, self.n_cand = torch.zeros((D + 1, 1), **f32), torch.zeros((1,), **i32)
+        self.seg_cnt = torch.zeros((D, S), **i32)
+        hx, hz = np.asarray([1, 1, -1, -1, 1, 1, -1, -1]) * 0.5, np.asarray([1, -1, -1, 1, 1, -1, -1, 1]) * 0.5
+        hy = np.asarray([1, 1, 1, 1, -1, -1, -1, -1]) * 0.5
+        self.pred_box3d, self.pred_angle, self.pred_size = torch.zeros((D + 1, 24), **f64), torch.zeros((D + 1,), **f64), torch.zeros((D + 1, 3), **f64)
+        self.pred_box3d[D] = torch.from_numpy(np.stack([hx, hy, hz], 1).reshape(24)).to(dev)
+        self.pred_size[D] = 1.0
+        self.slot_unit, self.n_kept = torch.full((B,), D, **i32), torch.zeros((1,), **i32)
+        self.seg_off, self.off, self.counts = torch.zeros((D * S + 1,), **i64), torch.zeros((B + 1,), **i64), torch.zeros((B,), **i64)
+        self.slot_class, self.slot_group, self.stage1_row = torch.zeros((B,), **i32), torch.full((B,), G, **i32), torch.full((B,), -1, **i32)
+        # the spare row is what an empty slot's all-zero choice row reads: fcn_prepare_inputs_refine indexes off[b] + choice
+        self.points = torch.zeros((capacity + 1, ps), **f32)
+        self.t = {"raw": self.points, "off": self.off, "choice": torch.zeros((B, N), **i32),
+                  "pcorners": torch.zeros((B, 24), **f64), "pangle": torch.zeros((B,), **f64), "psize": torch.zeros((B, 3), **f64),
+                  "coin": torch.zeros((B,), **f64), "normal": torch.zeros((B,), **f64)}
+        self.out = builder.alloc(B, lpad, False)
+        if builder.one_hot:
+            self.out["one_hot"] = torch.zeros((B, C), **f32)
+        self.out["rgb_prob"] = torch.zeros((B, 1), **f32)
+        self.batch = {k: v for k, v in self.out.items() if k != "lens"}      # what stage2.detect takes (as detect() passes it)
+        self.res = {"dets": torch.zeros((B * lpad[1], 8), **f32), "valid": torch.zeros((B * lpad[1],), **i32),
+                    "keep": torch.full((G, top_k), -1, **i32), "cnt": torch.zeros((G,), **i32)}
+
+    def set_units(self, frustum_frame, types, unit_group=None):
+        """Fills unit_frame / unit_class / unit_group in place from host sequences of length B1 (validated here: frames in [0, F),
+        class names of refine_builder.classes, groups in [0, G); unit_group None: every frustum its own group, which needs
+        G >= B1).  An upload: not for a captured region."""
+        who = "CascadeLink.set_units"
+        fr = np.asarray(torch.as_tensor(frustum_frame).cpu().numpy()).reshape(-1)
+        ug = np.arange(self.B1) if unit_group is None else np.asarray(torch.as_tensor(unit_group).cpu().numpy()).reshape(-1)
+        types = [str(t) for t in types]
+        if len(fr) != self.B1 or len(ug) != self.B1 or len(types) != self.B1:
+            raise ValueError("%s: %d frustums, got %d frames, %d types, %d groups" % (who, self.B1, len(fr), len(types), len(ug)))
+        if fr.dtype.kind not in "iu" or ug.dtype.kind not in "iu" or fr.min() < 0 or fr.max() >= self.F or ug.min() < 0 or ug.max() >= self.G:
+            raise ValueError("%s: frames must be integers in [0, %d) and groups integers in [0, %d)" % (who, self.F, self.G))
+        cls = [self.builder.classes.index(t) if t in self.builder.classes else -1 for t in types]
+        if min(cls) < 0:
+            raise ValueError("%s: type %r is not one of %r" % (who, types[cls.index(-1)], tuple(self.builder.classes)))
+        for dst, src in ((self.unit_frame, fr), (self.unit_class, cls), (self.unit_group, ug)):
+            dst.copy_(torch.from_numpy(np.ascontiguousarray(np.asarray(src, dtype=np.int32))))
+        return self
+
+    def step(self, data_dicts):
+        """Enqueues on the current stream stage1.detect, candidates, count, plan, fill, the gathers through slot_unit, the draw,
+        fcn_prepare_inputs_refine and stage2.detect with the slots' groups and the spare group G -- and nothing else: no host read,
+        no upload (capturable).  data_dicts: the first-stage batch of B1 frustums at L2 windows on the second stride.
+        Returns a dict, the same tensors of the link every step: dets (B * lpad[1], 8), valid, keep (G, top_k), cnt (G) of the
+        second stage (an empty slot's rows belong to the spare group: no keep entry points at them), stage1_row (B) int32 the
+        first-stage row each slot refines (-1: empty), n_kept (1) the filled slots; for inspection batch (the second stage's
+        input), slot_unit (B) the candidate of each slot (D: empty), cand_row (D+1) / n_cand (1) the candidate table, and stage1 =
+        the first stage's (dets, valid, keep, cnt) of this call.  check() reads the status words."""
+        L, dev, bld = _native.lib(), self.device, self.builder
+        G, D, B, S, t = self.G, self.D, self.B, self.S, self.t
+        p = lambda x: None if x is None else x.data_ptr()
+        pts, foff = self.frames
+        s1 = self.stage1.detect(data_dicts, unit_group=self.unit_group, num_groups=G, method=self.method, thresh=self.thresh,
+                                top_k=self.top_k)
+        dets1, _, keep1, cnt1 = s1
+        if tuple(dets1.shape) != (self.R, 8) or tuple(keep1.shape) != (G, self.top_k):      # (attributes: nothing is read)
+            raise ValueError("CascadeLink.step: the first-stage batch must hold %d frustums of %d windows" % (self.B1, self.L2))
+        with torch.cuda.device(dev):
+            s = _native.current_stream(dev)
+            _native.check(L.fcn_cascade_candidates(p(keep1), p(cnt1), G, self.top_k, self.L2, p(self.unit_frame), p(self.unit_class),
+                                                   p(self.unit_group), self.B1, p(dets1), self.R, D, p(self.cand_row), p(self.cand_frame),
+                                                   p(self.cand_class), p(self.cand_group), p(self.cand_score), p(self.n_cand),
+                                                   p(self.status), s), "fcn_cascade_candidates")
+            args = (p(pts), p(foff), self.F, self.ps, p(dets1), self.R, p(self.cand_row), p(self.cand_frame), D, self.ratio, S)
+            _native.check(L.fcn_refine_detect_count(*args, p(self.seg_cnt), p(self.pred_box3d), p(self.pred_angle), p(self.pred_size), s),
+                          "fcn_refine_detect_count")
+            _native.check(L.fcn_refine_detect_plan(p(self.seg_cnt), p(self.pred_size), self.strides_c, self.lpad_c, D, S, B, self.capacity,
+                                                   p(self.slot_unit), p(self.n_kept), p(self.seg_off), p(self.off), p(self.counts),
+                                                   p(self.status), s), "fcn_refine_detect_plan")
+            _native.check(L.fcn_refine_detect_fill(*args, p(self.seg_off), p(self.points), s), "fcn_refine_detect_fill")
+            for src, dst in ((self.pred_box3d, t["pcorners"]), (self.pred_angle, t["pangle"]), (self.pred_size, t["psize"]),
+                             (self.cand_class, self.slot_class), (self.cand_score, self.out["rgb_prob"]),
+                             (self.cand_group, self.slot_group), (self.cand_row, self.stage1_row)):
+                torch.index_select(src, 0, self.slot_unit, out=dst)
+            if "one_hot" in self.out:
+                torch.index_select(self.eye, 0, self.slot_class, out=self.out["one_hot"])
+            self.draws.draw(self.counts, bld.npoints, False, False, out=(t["choice"], t["coin"], t["normal"]))
+            bld.launch(t, self.out, self.ps, self.lpad, False)
+        d2, v2, k2, c2 = self.stage2.detect(self.batch, unit_group=self.slot_group, num_groups=G + 1, method=self.method,
+                                            thresh=self.thresh, top_k=self.top_k)
+        res = self.res
+        res["dets"].copy_(d2); res["valid"].copy_(v2); res["keep"].copy_(k2[:G]); res["cnt"].copy_(c2[:G])
+        return {"dets": res["dets"], "valid": res["valid"], "keep": res["keep"], "cnt": res["cnt"], "stage1_row": self.stage1_row,
+                "n_kept": self.n_kept, "stage1": s1, "batch": self.batch, "slot_unit": self.slot_unit, "cand_row": self.cand_row,
+                "n_cand": self.n_cand}
+
+    def check(self):
+        """Reads the status words of the link and of its draws (a synchronisation: not for a captured region); raises ValueError
+        naming the bits set since the last check() and clears them.  Bit 0 is the draws' own: an EMPTY slot has no row to draw
+        from either, so it is set by every step with fewer survivors than slots."""
+        words = (self.status, self.draws.status)
+        s = 0
+        for v in torch.cat(words).cpu().tolist():
+            s |= int(v)
+        if s:
+            for w in words:
+                w.zero_()
+            raise ValueError("CascadeLink: status %d -- %s" % (s, "; ".join(text for bit, text in STATUS_BITS if s & bit)))
+
+
 class TwoStageDetector:
     """stage1, stage2: two PointNetDet models in eval mode, each built by the caller under its own configuration (cfg is
     global: build one, then the other); refine_builder: the RefineInputBuilder of the second stage's configuration;
@@ -401,6 +582,17 @@ class TwoStageDetector:
 
     def __init__(self, stage1, stage2, refine_builder, input_builder=None):
         self.stage1, self.stage2, self.refine_builder, self.input_builder = stage1, stage2, refine_builder, input_builder
+
+    def link(self, frame_points, frame_off, frustum_frame, types, B1, L2, D, B, capacity, lpad, seed, method, thresh, unit_group=None,
+             num_groups=None, top_k=300, ratio=1.2):
+        """detect() as one capturable sequence of launches at fixed sizes: a CascadeLink over this detector's two stages and
+        refine builder, its frustum tables filled from frustum_frame (B1) / types (B1) / unit_group (B1; default: every frustum its
+        own group) as detect() takes them.  link(...).step(data_dicts) then stands where detect(data_dicts, ...) stood."""
+        if num_groups is None:
+            num_groups = int(B1) if unit_group is None else int(torch.as_tensor(unit_group).max()) + 1
+        lk = CascadeLink(self.stage1, self.stage2, self.refine_builder, frame_points, frame_off, B1, L2, num_groups, top_k, D, B,
+                         capacity, lpad, seed, method, thresh, ratio)
+        return lk.set_units(frustum_frame, types, unit_group)
 
     def detect_frames(self, frame_points_velo, frame_off, calib, img_size, boxes2d, box_frame, types, prob, method, thresh,
                       unit_group=None, num_groups=None, top_k=300, ratio=1.2, draws=None, refine_draws=None,

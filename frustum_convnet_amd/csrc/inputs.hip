@@ -492,3 +492,9 @@ extern "C" int fcn_prepare_inputs_refine(const fcn_inp_refine_desc *d, const flo
 // box jitter drawn on the device and the one-workgroup plan between count and fill (fcn_refine_train_match / _count / _fill,
 // fcn_box3d_jitter_draw, fcn_refine_train_plan): csrc/refine_plan.h
 #include "refine_plan.h"
+
+// ------------------------------------------------------------------------------------------------
+// Two-stage inference without a host read: the first stage's keep lists to a candidate table, the selection of refine_select.h on
+// the segmented grid without its read-backs, and the training plan's kernel between count and fill (fcn_cascade_candidates,
+// fcn_refine_detect_count / _plan / _fill): csrc/cascade_plan.h
+#include "cascade_plan.h"

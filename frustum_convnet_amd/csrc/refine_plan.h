@@ -17,6 +17,8 @@
 // Status bits (one int32 word, OR-ed, never cleared here): FP_ST_FEW fewer than B survivors; FP_ST_TRUNC rows dropped because the
 // total exceeds the capacity; RP_ST_WIDE a unit with positives whose predicted width needs more windows than lpad on some stride;
 // RP_ST_WIDTH a unit with positives whose predicted width is not a positive finite number (bit 0 is DeviceDraws').
+// rp_plan_kernel<true> is the plan of the inference link (cascade_plan.h): the same kernel, told that too few survivors is the normal
+// case there and too many the one to report (RP_ST_MANY instead of FP_ST_FEW).
 #pragma once
 #include "draws.h"
 #include "refine_label.h"
@@ -24,6 +26,7 @@
 
 #define RP_ST_WIDE 32                  // bit 5
 #define RP_ST_WIDTH 64                 // bit 6
+#define RP_ST_MANY 256                 // bit 8: more survivors than slots (the inference link alone)
 
 struct RpJitterArgs {
     int U;
@@ -68,7 +71,7 @@ struct RpPlanArgs {
     int32_t *status;
 };
 
-__global__ __launch_bounds__(FP_T) void rp_plan_kernel(RpPlanArgs a)
+template <bool DETECT> __global__ __launch_bounds__(FP_T) void rp_plan_kernel(RpPlanArgs a)
 {
     __shared__ int32_t sslot[FP_MAX_D];                     // unit -> its slot, -1 without one
     __shared__ int64_t slo[FP_MAX_D], shi[FP_MAX_D];        // slot -> its clamped first row and the clamped end of its rows
@@ -137,7 +140,8 @@ __global__ __launch_bounds__(FP_T) void rp_plan_kernel(RpPlanArgs a)
         a.off[B] = end;
         a.soff[M] = end;
         a.n_kept[0] = n;
-        const int st2 = (survivors < B ? FP_ST_FEW : 0) | (total > a.cap ? FP_ST_TRUNC : 0);
+        const int few = DETECT ? (survivors > B ? RP_ST_MANY : 0) : (survivors < B ? FP_ST_FEW : 0);
+        const int st2 = few | (total > a.cap ? FP_ST_TRUNC : 0);
         if (st2) atomicOr(a.status, st2);
     }
 }
@@ -195,10 +199,11 @@ extern "C" int fcn_box3d_jitter_draw(int D, int A, uint64_t seed, const int64_t 
     return 0;
 }
 
-extern "C" int fcn_refine_train_plan(const int32_t *seg_cnt, const int32_t *seg_pos, const double *pred_size, const double *stride,
-                                     const int32_t *lpad, int U, int S, int B, int64_t capacity, int32_t *slot_unit,
-                                     int32_t *n_kept, int64_t *seg_off, int64_t *off, int64_t *counts, int32_t *status,
-                                     void *stream)
+// the argument checks and the launch fcn_refine_train_plan and fcn_refine_detect_plan (cascade_plan.h) share
+template <bool DETECT>
+static inline int rp_plan_launch(const int32_t *seg_cnt, const int32_t *seg_pos, const double *pred_size, const double *stride,
+                                 const int32_t *lpad, int U, int S, int B, int64_t capacity, int32_t *slot_unit, int32_t *n_kept,
+                                 int64_t *seg_off, int64_t *off, int64_t *counts, int32_t *status, void *stream)
 {
     if (!seg_cnt || !seg_pos || !pred_size || !stride || !lpad || !slot_unit || !n_kept || !seg_off || !off || !counts || !status)
         return FCN_E_BADARG;
@@ -211,7 +216,16 @@ extern "C" int fcn_refine_train_plan(const int32_t *seg_cnt, const int32_t *seg_
     for (int s = 0; s < 4; ++s) { a.stride[s] = stride[s]; a.lpad[s] = lpad[s]; }
     a.U = U; a.S = S; a.B = B; a.cap = capacity;
     a.slot_unit = slot_unit; a.n_kept = n_kept; a.soff = seg_off; a.off = off; a.counts = counts; a.status = status;
-    hipLaunchKernelGGL(rp_plan_kernel, dim3(1), dim3(FP_T), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(rp_plan_kernel<DETECT>, dim3(1), dim3(FP_T), 0, (hipStream_t)stream, a);
     FCN_CHECK_LAUNCH();
     return 0;
+}
+
+extern "C" int fcn_refine_train_plan(const int32_t *seg_cnt, const int32_t *seg_pos, const double *pred_size, const double *stride,
+                                     const int32_t *lpad, int U, int S, int B, int64_t capacity, int32_t *slot_unit,
+                                     int32_t *n_kept, int64_t *seg_off, int64_t *off, int64_t *counts, int32_t *status,
+                                     void *stream)
+{
+    return rp_plan_launch<false>(seg_cnt, seg_pos, pred_size, stride, lpad, U, S, B, capacity, slot_unit, n_kept, seg_off, off, counts,
+                                 status, stream);
 }

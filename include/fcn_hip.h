@@ -1048,6 +1048,49 @@ int fcn_refine_train_plan(const int32_t *seg_cnt, const int32_t *seg_pos, const 
                           int64_t *seg_off, int64_t *off, int64_t *counts, int32_t *status, void *stream);
 int fcn_refine_train_plan_limits(int *max_u, int *max_segs);
 
+/* ---------------------------------------------------------------------------------------------
+ * Two-stage inference with no host read between its launches (csrc/cascade_plan.h; INTEGRATION.md "Capturable two-stage inference"
+ * states the contract bit for bit, tests/cascade_plan_ref.py restates it in numpy): candidates, count, plan, fill -- none of them
+ * reads anything back, allocates or synchronises, so the sequence can be captured into a hipGraph.  Status bits (*status: one int32
+ * on the device, OR-ed, never cleared here): bit 2 (4), bit 5 (32), bit 6 (64) as fcn_refine_train_plan sets them; bit 7 (128) more
+ * first-stage kept rows than D; bit 8 (256) more surviving candidates than B; bit 9 (512) a first-stage group with cnt < 0 (the NMS
+ * overflowed) or cnt > top_k.  (Bit 0 is fcn_draw_batch's; bit 1 is never set: fewer survivors than B is the normal case here.)
+ *
+ * fcn_cascade_candidates: keep (G, top_k) / cnt (G) int32 as fcn_rotate_nms_3d writes them -> the first D kept rows in the order
+ * "groups ascending, keep order inside a group".  For kept row r of frustum u = r / L2: cand_row = r, cand_frame = unit_frame[u],
+ * cand_class = unit_class[u], cand_group = unit_group[u] (unit_* (B1) int32), cand_score = dets[r * 8 + 7] (dets (R, 8) fp32);
+ * *n_cand = the rows written, at most D.  Rows n_cand..D-1 get the filler: row -1, frame -1, class 0, group G, score 0 (a candidate
+ * the count skips, of the spare group).  A group with cnt < 0 or cnt > top_k contributes nothing and sets bit 9; a keep entry
+ * outside [0, R), or with r / L2 outside [0, B1), is skipped; none of them is dereferenced.  More kept rows than D: the rest are
+ * dropped, bit 7.  One workgroup, an order-preserving prefix sum, no atomics on the data.  Every output is written on every call.
+ * NULL pointers or G, top_k, L2, B1, R or D < 1: FCN_E_BADARG; G > 65536 or D > 2048: FCN_E_LIMIT; nothing written. */
+int fcn_cascade_candidates(const int32_t *keep, const int32_t *cnt, int G, int top_k, int L2, const int32_t *unit_frame,
+                           const int32_t *unit_class, const int32_t *unit_group, int B1, const float *dets, int R, int D,
+                           int32_t *cand_row, int32_t *cand_frame, int32_t *cand_class, int32_t *cand_group, float *cand_score,
+                           int32_t *n_cand, int32_t *status, void *stream);
+/* fcn_refine_detect_count / _fill: the selection of fcn_refine_select_count / _fill -- the same closed fp64 box, the same
+ * pred_corners / pred_angle / pred_size, the same stored rows bit for bit -- on a grid of (S, D) workgroups, workgroup (s, d)
+ * scanning rows [s * seg, (s + 1) * seg) of candidate d's frame (seg = fcn_frustum_select_seg()), and without the read-back of
+ * cand_row / cand_frame.  count writes seg_cnt (D, S) int32; fill takes seg_off (D*S+1) int64, the exclusive prefix sum over the
+ * flattened counts (fcn_refine_detect_plan's), which bounds every store.  A candidate whose row is outside [0, R) or whose frame is
+ * outside [0, F) is skipped silently: its counts are 0, nothing of it is dereferenced or written, the calls return 0.  "No frame is
+ * longer than S * seg rows" is the caller's duty: rows beyond S segments would silently not be searched.
+ * pt_stride < 3, D, F or R < 0, D > 65535, S < 1 or a NULL pointer: FCN_E_BADARG, nothing written.  D == 0: nothing to do; F == 0:
+ * the counts are zeroed. */
+int fcn_refine_detect_count(const float *frame_pts, const int64_t *frame_off, int F, int pt_stride, const float *dets, int R,
+                            const int32_t *cand_row, const int32_t *cand_frame, int D, double ratio, int S, int32_t *seg_cnt,
+                            double *pred_corners, double *pred_angle, double *pred_size, void *stream);
+int fcn_refine_detect_fill(const float *frame_pts, const int64_t *frame_off, int F, int pt_stride, const float *dets, int R,
+                           const int32_t *cand_row, const int32_t *cand_frame, int D, double ratio, int S, const int64_t *seg_off,
+                           float *out_pts, void *stream);
+/* fcn_refine_detect_plan: fcn_refine_train_plan (its kernel) with seg_cnt as seg_pos -- the reference's lidar_point_threshold = 1: a
+ * candidate without a selected row takes no slot -- and U = D.  Same width rules, slots, seg_off, off and STORED counts, same
+ * refusals and limits.  Two status differences: fewer survivors than B sets nothing, more survivors than B (the rest are dropped)
+ * sets bit 8. */
+int fcn_refine_detect_plan(const int32_t *seg_cnt, const double *pred_size, const double *stride, const int32_t *lpad, int D, int S,
+                           int B, int64_t capacity, int32_t *slot_unit, int32_t *n_kept, int64_t *seg_off, int64_t *off,
+                           int64_t *counts, int32_t *status, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
