@@ -99,7 +99,9 @@ EXPORTS = ("fcn_arch", "fcn_build_hash", "fcn_stat_replicas", "fcn_query_depth_p
            "fcn_frustum_sunrgbd_train_plan", "fcn_frustum_subsample_draw", "fcn_frustum_sunrgbd_train_slots", "fcn_draw_batch_sliced",
            "fcn_refine_train_match", "fcn_refine_train_count", "fcn_refine_train_fill", "fcn_box3d_jitter_draw", "fcn_refine_train_plan",
            "fcn_refine_train_plan_limits",
-           "fcn_cascade_candidates", "fcn_refine_detect_count", "fcn_refine_detect_fill", "fcn_refine_detect_plan")
+           "fcn_cascade_candidates", "fcn_refine_detect_count", "fcn_refine_detect_fill", "fcn_refine_detect_plan",
+           "fcn_frustum_detect_count", "fcn_frustum_detect_fill", "fcn_frustum_detect_plan", "fcn_frustum_detect_plan_limits",
+           "fcn_frustum_fov_plan")
 
 _lib = None
 
@@ -346,6 +348,18 @@ def lib():
         L.fcn_refine_detect_plan.restype = ctypes.c_int
         L.fcn_refine_detect_plan.argtypes = ([c_fp] * 2 + [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int32)] +
                                              [ctypes.c_int] * 3 + [ctypes.c_int64] + [c_fp] * 7)
+    if hasattr(L, "fcn_frustum_detect_plan") or "FCN_LIB_NAME" not in os.environ:
+        L.fcn_frustum_detect_count.restype = ctypes.c_int
+        L.fcn_frustum_detect_count.argtypes = fs_in + [c_fp] * 5
+        L.fcn_frustum_detect_fill.restype = ctypes.c_int
+        L.fcn_frustum_detect_fill.argtypes = fs_in + [c_fp] * 4
+        L.fcn_frustum_detect_plan.restype = ctypes.c_int
+        L.fcn_frustum_detect_plan.argtypes = ([c_fp] * 4 + [ctypes.c_double] * 2 + [ctypes.c_int] * 3 + [ctypes.c_int64, ctypes.c_int] +
+                                              [c_fp] * 7)
+        L.fcn_frustum_detect_plan_limits.restype = ctypes.c_int
+        L.fcn_frustum_detect_plan_limits.argtypes = [ctypes.POINTER(ctypes.c_int)] * 2
+        L.fcn_frustum_fov_plan.restype = ctypes.c_int
+        L.fcn_frustum_fov_plan.argtypes = [c_fp, ctypes.c_int, ctypes.c_int, ctypes.c_int64, c_fp, c_fp, c_fp]
     L.fcn_rotate_nms_3d.restype = ctypes.c_int
     L.fcn_rotate_nms_3d.argtypes = [c_fp] * 3 + [ctypes.c_int] * 3 + [ctypes.c_float, ctypes.c_int] + [c_fp] * 3
     _lib = L

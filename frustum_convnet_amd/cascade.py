@@ -9,7 +9,8 @@ stages the host reads the first stage's keep lists, D point counts and D predict
 reads the 2 * D candidate indices back to range-check them (five small reads that wait for the stream; no point data).  No CPU
 fallback.  CascadeLink (TwoStageDetector.link) is the same link as ONE capturable sequence of launches at a fixed number of
 candidates, a fixed batch size and fixed window counts, with no host read (C-ABI fcn_cascade_candidates, fcn_refine_detect_count /
-_plan / _fill, csrc/cascade_plan.h).
+_plan / _fill, csrc/cascade_plan.h).  FrameCascade (TwoStageDetector.frame_link) puts frustum.FrameDetectSource in front of it:
+velodyne frames and a resident table of 2-D detections to second-stage detections, what detect_frames does, as one such sequence.
 
 Training the refinement stage on the first stage's output (extract_frustum_det_data :406-592: match to the labels, enlarge, jitter,
 select, count the positives, reject) is match_detections + draw_box3d_jitter + refine_training_candidates (C-ABI fcn_refine_match,
@@ -193,7 +194,8 @@ STATUS_BITS = ((1, "bit 0: a slot had no row to draw from (its choice row is zer
                (64, "bit 6: a unit's predicted width is not a positive finite number (the unit was dropped)"),
                (128, "bit 7: the first stage kept more rows than the link has candidates (the rest were dropped)"),
                (256, "bit 8: more candidates survived than the batch has slots (the rest were dropped)"),
-               (512, "bit 9: a first-stage group overflowed the NMS (cnt = -1) or reports cnt > top_k (it was passed on to nobody)"))
+               (512, "bit 9: a first-stage group overflowed the NMS (cnt = -1) or reports cnt > top_k (it was passed on to nobody)"),
+               (1024, "bit 10: n_boxes lies outside [0, D] or a box's frame outside [0, F) (the overflow or the box was ignored)"))
 
 
 class RefineTrainSource:
@@ -575,6 +577,61 @@ class CascadeLink:
             raise ValueError("CascadeLink: status %d -- %s" % (s, "; ".join(text for bit, text in STATUS_BITS if s & bit)))
 
 
+class FrameCascade:
+    """Resident velodyne frames and a resident table of 2-D detections -> second-stage detections with no host read, no upload and no
+    validation per step: what TwoStageDetector.detect_frames does, as ONE sequence of launches that can be captured into a hipGraph
+    and replayed on boxes and points overwritten in place (INTEGRATION.md "Capturable inference front" states the contract).  A
+    frustum.FrameDetectSource(fov=True) wired to a CascadeLink:
+      * the link searches source.fov_points, built on the VELODYNE frame_off as the worst case -- a frame's image-FOV subset is no
+        longer than the frame, so the link's S and its row check hold for every later step;
+      * the source writes the frames' FOV offsets into link.frame_off (the link holds ONE offsets tensor: link.frames[1] is the same
+        object) and the slots' frame, class and group into link.unit_frame / unit_class / unit_group;
+      * spare_group = G: the first stage runs its NMS over groups 0..G-1 and a group only takes units of its own number, so an empty
+        first-stage slot never reaches a keep list, hence never the candidate table.
+    stage1, stage2, refine_builder, G, top_k, D, B, capacity, lpad, method, thresh, ratio: as CascadeLink takes them; input_builder,
+    frame_points, frame_off, calib, img_size, B1, D1 (rows of the detection table), capacity1 (rows of the first stage's point buffer),
+    clip_distance, clip_boxes, img_height_threshold, lidar_point_threshold: as FrameDetectSource takes them; seed keys the source's
+    draws, seed + 1 the link's.  .source and .link are the two parts; fill the table with source.set_boxes() or in place."""
+
+    def __init__(self, stage1, stage2, input_builder, refine_builder, frame_points, frame_off, calib, img_size, B1, D1, capacity1, G,
+                 top_k, D, B, capacity, lpad, seed, method, thresh, ratio=1.2, clip_distance=2.0, clip_boxes=True,
+                 img_height_threshold=5, lidar_point_threshold=1):
+        from .frustum import FrameDetectSource
+        if tuple(input_builder.classes) != tuple(refine_builder.classes):
+            raise ValueError("FrameCascade: the two builders must share their classes, got %r and %r" %
+                             (tuple(input_builder.classes), tuple(refine_builder.classes)))
+        self.source = FrameDetectSource(frame_points, frame_off, calib, img_size, input_builder, B1, D1, capacity1, seed, int(G),
+                                        clip_distance, clip_boxes, img_height_threshold, lidar_point_threshold, fov=True)
+        src = self.source
+        self.link = CascadeLink(stage1, stage2, refine_builder, src.fov_points, src.frames[1].cpu().clone(), B1, input_builder.L[1], G, top_k, D,
+                                B, capacity, lpad, int(seed) + 1, method, thresh, ratio)
+        lk = self.link
+        src.bind(fov_off=lk.frame_off, slot_frame=lk.unit_frame, slot_class=lk.unit_class, slot_group=lk.unit_group)
+        self.keys = ("point_cloud", "rot_angle", "rgb_prob", "one_hot", "center_ref1", "center_ref2", "center_ref3", "center_ref4")
+
+    def step(self):
+        """source.step() followed by link.step() on its batch, on the current stream (capturable).  Returns the link's dict plus
+        slot_box (B1) the box of each first-stage slot (D1: empty), n_kept1 (1) the filled first-stage slots and batch1, the first
+        stage's input; the same tensors every step."""
+        got = self.source.step()
+        batch = {k: got[k] for k in self.keys if k in got}
+        res = self.link.step(batch)
+        res.update(slot_box=got["slot_box"], n_kept1=got["n_kept"], batch1=batch)
+        return res
+
+    def check(self):
+        """check() of both parts in one: reads their status words (a synchronisation), raises ValueError naming the bits set since
+        the last check() and clears them."""
+        words = (self.source.status, self.source.draws.status, self.link.status, self.link.draws.status)
+        s = 0
+        for v in torch.cat(words).cpu().tolist():
+            s |= int(v)
+        if s:
+            for w in words:
+                w.zero_()
+            raise ValueError("FrameCascade: status %d -- %s" % (s, "; ".join(text for bit, text in STATUS_BITS if s & bit)))
+
+
 class TwoStageDetector:
     """stage1, stage2: two PointNetDet models in eval mode, each built by the caller under its own configuration (cfg is
     global: build one, then the other); refine_builder: the RefineInputBuilder of the second stage's configuration;
@@ -593,6 +650,19 @@ class TwoStageDetector:
         lk = CascadeLink(self.stage1, self.stage2, self.refine_builder, frame_points, frame_off, B1, L2, num_groups, top_k, D, B,
                          capacity, lpad, seed, method, thresh, ratio)
         return lk.set_units(frustum_frame, types, unit_group)
+
+    def frame_link(self, frame_points_velo, frame_off, calib, img_size, B1, D1, capacity1, num_groups, D, B, capacity, lpad, seed,
+                   method, thresh, top_k=300, ratio=1.2, clip_distance=2.0, clip_boxes=True, img_height_threshold=5,
+                   lidar_point_threshold=1):
+        """detect_frames() as one capturable sequence of launches at fixed sizes: a FrameCascade over this detector's two stages and
+        builders -- the arguments of link() and of frustum.FrameDetectSource together; the boxes, their frames, types, scores and
+        groups go into the returned cascade's detection table (.source.set_boxes(...), or in place).  frame_link(...).step() then
+        stands where detect_frames(...) stood."""
+        if self.input_builder is None:
+            raise ValueError("TwoStageDetector.frame_link needs the first stage's InputBuilder (input_builder=...)")
+        return FrameCascade(self.stage1, self.stage2, self.input_builder, self.refine_builder, frame_points_velo, frame_off, calib,
+                            img_size, B1, D1, capacity1, num_groups, top_k, D, B, capacity, lpad, seed, method, thresh, ratio,
+                            clip_distance, clip_boxes, img_height_threshold, lidar_point_threshold)
 
     def detect_frames(self, frame_points_velo, frame_off, calib, img_size, boxes2d, box_frame, types, prob, method, thresh,
                       unit_group=None, num_groups=None, top_k=300, ratio=1.2, draws=None, refine_draws=None,

@@ -498,3 +498,10 @@ extern "C" int fcn_prepare_inputs_refine(const fcn_inp_refine_desc *d, const flo
 // the segmented grid without its read-backs, and the training plan's kernel between count and fill (fcn_cascade_candidates,
 // fcn_refine_detect_count / _plan / _fill): csrc/cascade_plan.h
 #include "cascade_plan.h"
+
+// ------------------------------------------------------------------------------------------------
+// The inference front without a host read: frames + a resident table of 2-D detections -> the first-stage batch's raw points at a
+// fixed number of slots and the second stage's image-FOV search set -- the selection of frustum_select.h behind a device-resident
+// box count, without its read-backs, and the one-workgroup plans between count and fill (fcn_frustum_detect_count / _plan / _fill,
+// fcn_frustum_fov_plan): csrc/frustum_detect_plan.h
+#include "frustum_detect_plan.h"

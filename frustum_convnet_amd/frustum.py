@@ -15,7 +15,10 @@ point buffer) and each entry point reads box_frame and frame_off back to range-c
 FrameTrainSource (at the end) is the KITTI training path again with NOTHING read back: frames and labels resident, boxes perturbed
 on the device, a one-workgroup plan in place of the host's kept list and prefix sum, a fixed batch size -- capturable
 (fcn_box2d_perturb, fcn_frustum_train_count / _plan / _fill, csrc/frustum_plan.h).  SunrgbdTrainSource is the same for the SUN-RGBD
-training path, with the frustum subsamples drawn on the device as well (csrc/frustum_sunrgbd_plan.h).
+training path, with the frustum subsamples drawn on the device as well (csrc/frustum_sunrgbd_plan.h).  FrameDetectSource is the
+KITTI INFERENCE path the same way: resident frames and a resident table of 2-D detections -> the first-stage batch at a fixed number
+of slots and, when asked, the image-FOV search set of the second stage (fcn_frustum_detect_count / _plan / _fill,
+fcn_frustum_fov_plan, csrc/frustum_detect_plan.h).
 No CPU fallback.
 """
 import ctypes
@@ -409,7 +412,9 @@ def sunrgbd_training_candidates(frame_points, frame_off, K, Rtilt, boxes2d, box_
 STATUS_BITS = ((1, "bit 0: a slot had no row to draw from (its choice row is zeros)"),
                (2, "bit 1: fewer boxes survived than the batch has slots (the empty slots repeat box 0's labels over no rows)"),
                (4, "bit 2: the selected rows exceed the capacity of the point buffer (the overflow was dropped)"),
-               (16, "bit 4: a box had no valid perturbation within the attempt cap (its label box was used as it is)"))
+               (16, "bit 4: a box had no valid perturbation within the attempt cap (its label box was used as it is)"),
+               (256, "bit 8: more boxes survived than the batch has slots (the rest were dropped)"),
+               (1024, "bit 10: n_boxes lies outside [0, D] or a box's frame outside [0, F) (the overflow or the box was ignored)"))
 
 
 class FrameTrainSource:
@@ -812,3 +817,199 @@ class SunrgbdTrainSource:
             for w in words:
                 w.zero_()
             raise ValueError("SunrgbdTrainSource: status %d -- %s" % (s, "; ".join(text for bit, text in STATUS_BITS if s & bit)))
+
+
+# ------------------------------------------------------------------------------------------------
+# The KITTI first stage's INFERENCE input as ONE capturable sequence of launches (csrc/frustum_detect_plan.h)
+class FrameDetectSource:
+    """Resident velodyne frames and a resident table of at most D 2-D detections -> the InputBuilder inference batch at a FIXED
+    batch size B1, every step, with no host read and no upload: what frustum_candidates + InputBuilder.build_device (+
+    image_fov_points with fov=True) do behind their synchronisations, as one sequence of launches that can be captured into a
+    hipGraph and replayed on boxes and points overwritten in place (INTEGRATION.md "Capturable inference front" states the contract).
+    frame_points: a contiguous (n >= 1, >= 3) float32 device tensor, HELD, not copied -- a caller may overwrite it in place between
+    steps; frame_off, calib, img_size as frustum_candidates takes them (copied to the device; S, the segments of the longest frame,
+    is fixed here: frames written later must not be longer than S * fcn_frustum_select_seg() rows, nor move their offsets);
+    builder: an InputBuilder; B1: slots of the batch; D: rows of the detection table (B1 <= D <= 2048; survivors beyond B1, in box
+    order, are dropped and flagged); capacity: rows of the point buffer (rows beyond it are dropped and flagged); seed: keys the
+    DeviceDraws of the per-sample resample, one step further after every step(); spare_group: the group of an empty slot.
+    The detection table has D + 1 rows: boxes2d (D+1,4) fp64 xmin ymin xmax ymax, box_frame, box_class (index into builder.classes),
+    box_group (D+1) int32, box_prob (D+1) fp32 and n_boxes (1) int32, the live rows.  A 2-D detector overwrites rows 0..n_boxes-1 and
+    n_boxes in place between steps; set_boxes() fills them from host sequences.  Row D is the spare row an empty slot gathers -- a
+    unit box, frame 0, class 0, spare_group, probability 0 -- written here once: leave it alone.
+    fov=True: step() also selects every frame's image-FOV subset in rect camera coordinates into fov_points (n + 1, stride) /
+    fov_off (F+1), as image_fov_points returns them (rows behind fov_off[F] are stale).
+    Everything is validated here, once, on the host; step() validates nothing and reads nothing."""
+
+    def __init__(self, frame_points, frame_off, calib, img_size, builder, B1, D, capacity, seed, spare_group, clip_distance=2.0,
+                 clip_boxes=True, img_height_threshold=5, lidar_point_threshold=1, fov=False):
+        from .inputs import DeviceDraws
+        who = "FrameDetectSource"
+        if not (isinstance(frame_points, torch.Tensor) and frame_points.is_cuda and frame_points.dtype == torch.float32 and
+                frame_points.is_contiguous() and frame_points.dim() == 2 and frame_points.shape[0] >= 1 and not frame_points.requires_grad):
+            raise ValueError("%s: frame_points must be a contiguous (n >= 1, >= 3) float32 device tensor (it is held, not copied)" % who)
+        pts, foff, F, ps, S = _frames(who, frame_points, frame_off, resident=True)
+        dev = frame_points.device
+        P, V2C, R0, wh = _calib(calib, img_size, F, dev)
+        if builder.device.type != "cuda":
+            raise RuntimeError("frustum_convnet_amd: input construction is a HIP kernel (MI355X only); no CPU fallback")
+        B1, D, capacity, spare_group = int(B1), int(D), int(capacity), int(spare_group)
+        max_d, max_segs = self.limits()
+        if not (1 <= B1 <= D <= max_d):
+            raise ValueError("%s: need 1 <= B1 <= D <= %d, got B1 = %d, D = %d" % (who, max_d, B1, D))
+        if D * S > max_segs or (fov and F * S > max_segs):
+            raise ValueError("%s: D * S = %d * %d (fov: F * S = %d * %d) segments exceed the plan's %d" % (who, D, S, F, S, max_segs))
+        if capacity < 1:
+            raise ValueError("%s: capacity must be >= 1 row, got %d" % (who, capacity))
+        if not (0 <= spare_group < 2 ** 31):
+            raise ValueError("%s: spare_group must be a non-negative int32, got %d" % (who, spare_group))
+        hthr, pthr, clipd = float(img_height_threshold), float(lidar_point_threshold), float(clip_distance)
+        if not (np.isfinite(hthr) and np.isfinite(pthr) and np.isfinite(clipd)):
+            raise ValueError("%s: thresholds and clip_distance must be finite, got %r, %r, %r" %
+                             (who, img_height_threshold, lidar_point_threshold, clip_distance))
+        self.device, self.builder = dev, builder
+        self.B1, self.D, self.F, self.S, self.ps, self.capacity, self.spare_group = B1, D, F, S, ps, capacity, spare_group
+        self.clip_distance, self.clip_boxes, self.fov = clipd, bool(clip_boxes), bool(fov)
+        self.img_height_threshold, self.lidar_point_threshold = hthr, pthr
+        f32, f64, i32, i64 = (dict(dtype=t, device=dev) for t in (torch.float32, torch.float64, torch.int32, torch.int64))
+        N, C = builder.npoints, len(builder.classes)
+        # ---- resident: the frames (held), the calibration, the detection table with its spare row D
+        self.frames = (pts, foff, P, V2C, R0, wh)
+        self.boxes2d = torch.zeros((D + 1, 4), **f64)
+        self.boxes2d[D] = torch.tensor([0.0, 0.0, 1.0, 1.0], **f64)
+        self.box_frame, self.box_class = torch.zeros((D + 1,), **i32), torch.zeros((D + 1,), **i32)
+        self.box_group, self.box_prob = torch.full((D + 1,), spare_group, **i32), torch.zeros((D + 1,), **f32)
+        self.n_boxes = torch.zeros((1,), **i32)
+        self.eye = torch.eye(C, **f32)
+        self.draws = DeviceDraws(int(seed), builder.device)
+        self.status = torch.zeros((1,), **i32)
+        # ---- every intermediate.  The per-box outputs of the count have D + 1 rows as well: row D is what an empty slot gathers,
+        # the spare row's own box and a zero angle, written here once and never by a kernel
+        self.box2d, self.angle = torch.zeros((D + 1, 4), **f64), torch.zeros((D + 1,), **f64)
+        self.box2d[D] = self.boxes2d[D]
+        self.seg_cnt = torch.zeros((D, S), **i32)
+        self.slot_box, self.n_kept = torch.full((B1,), D, **i32), torch.zeros((1,), **i32)
+        self.slot_frame, self.slot_class = torch.zeros((B1,), **i32), torch.zeros((B1,), **i32)
+        self.slot_group = torch.full((B1,), spare_group, **i32)
+        self.seg_off, self.off, self.counts = torch.zeros((D * S + 1,), **i64), torch.zeros((B1 + 1,), **i64), torch.zeros((B1,), **i64)
+        # the spare row is what an empty slot's all-zero choice row reads: fcn_prepare_inputs_infer indexes off[b] + choice
+        self.points = torch.zeros((capacity + 1, ps), **f32)
+        self.t = {"raw": self.points, "off": self.off, "choice": torch.zeros((B1, N), **i32), "fangle": torch.zeros((B1,), **f64),
+                  "box2d": torch.zeros((B1, 4), **f64), "P": torch.zeros((B1, 12), **f64), "B": B1, "pt_stride": ps}
+        self.scalars = (torch.zeros((B1,), **f64), torch.zeros((B1,), **f64))          # the draw's coin and normal: unused
+        self.out = builder.alloc_infer(B1)
+        if self.fov:
+            # the whole-image selection: one box (0, 0, W, H) per frame, no clipping, every box live
+            n = int(pts.shape[0])
+            self.fov_boxes = torch.cat([torch.zeros((F, 2), **f64), wh], 1).contiguous()
+            self.fov_frame, self.fov_n = torch.arange(F, **i32), torch.full((1,), F, **i32)
+            self.fov_box2d, self.fov_angle = torch.zeros((F, 4), **f64), torch.zeros((F,), **f64)
+            self.fov_cnt, self.fov_seg_off = torch.zeros((F, S), **i32), torch.zeros((F * S + 1,), **i64)
+            self.fov_off = torch.zeros((F + 1,), **i64)
+            self.fov_points = torch.zeros((n + 1, ps), **f32)
+
+    @staticmethod
+    def limits():
+        """(the largest D, the largest D * S) of the plan."""
+        a, b = ctypes.c_int(0), ctypes.c_int(0)
+        _native.check(_native.lib().fcn_frustum_detect_plan_limits(ctypes.byref(a), ctypes.byref(b)), "fcn_frustum_detect_plan_limits")
+        return a.value, b.value
+
+    def bind(self, fov_off=None, slot_frame=None, slot_class=None, slot_group=None):
+        """Points outputs of step() at tensors of the caller (cascade.FrameCascade: the link's frame offsets and frustum tables):
+        fov_off (F+1) int64; slot_frame, slot_class, slot_group (B1) int32 -- contiguous device tensors, written from the next
+        step() on."""
+        for name, t, dtype, n in (("fov_off", fov_off, torch.int64, self.F + 1), ("slot_frame", slot_frame, torch.int32, self.B1),
+                                  ("slot_class", slot_class, torch.int32, self.B1), ("slot_group", slot_group, torch.int32, self.B1)):
+            if t is None:
+                continue
+            if not (isinstance(t, torch.Tensor) and t.device == self.device and t.dtype == dtype and t.is_contiguous() and
+                    tuple(t.shape) == (n,)) or (name == "fov_off" and not self.fov):
+                raise ValueError("FrameDetectSource.bind: %s must be a contiguous (%d,) %s tensor on %s" % (name, n, dtype, self.device))
+            setattr(self, name, t)
+        return self
+
+    def set_boxes(self, boxes2d, box_frame, types, prob, unit_group=None):
+        """Fills rows 0..n-1 of the detection table and n_boxes in place from host sequences of n <= D boxes (validated here: finite
+        boxes, frames in [0, F), class names of builder.classes, finite scores, groups in [0, spare_group); unit_group None: every
+        box its own group, which needs n <= spare_group).  An upload: not for a captured region."""
+        who = "FrameDetectSource.set_boxes"
+        host = lambda a: (a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a))
+        boxes = np.ascontiguousarray(host(boxes2d), dtype=np.float64).reshape(-1, 4)
+        fr, pr = np.ascontiguousarray(host(box_frame)).reshape(-1), np.ascontiguousarray(host(prob), dtype=np.float32).reshape(-1)
+        n = len(boxes)
+        ug = np.arange(n) if unit_group is None else np.ascontiguousarray(host(unit_group)).reshape(-1)
+        types = [str(t) for t in types]
+        if n > self.D or len(fr) != n or len(pr) != n or len(ug) != n or len(types) != n:
+            raise ValueError("%s: %d boxes (at most %d), %d frames, %d types, %d scores, %d groups" %
+                             (who, n, self.D, len(fr), len(types), len(pr), len(ug)))
+        if n and (fr.dtype.kind not in "iu" or ug.dtype.kind not in "iu" or fr.min() < 0 or fr.max() >= self.F or ug.min() < 0 or
+                  ug.max() >= self.spare_group):
+            raise ValueError("%s: frames must be integers in [0, %d) and groups integers in [0, %d)" % (who, self.F, self.spare_group))
+        if not (np.isfinite(boxes).all() and np.isfinite(pr).all()):
+            raise ValueError("%s: boxes and scores must be finite" % who)
+        cls = [self.builder.classes.index(t) if t in self.builder.classes else -1 for t in types]
+        if n and min(cls) < 0:
+            raise ValueError("%s: type %r is not one of %r" % (who, types[cls.index(-1)], tuple(self.builder.classes)))
+        up = lambda a, dt: torch.from_numpy(np.ascontiguousarray(np.asarray(a, dtype=dt)))
+        if n:
+            self.boxes2d[:n].copy_(up(boxes, np.float64))
+            self.box_prob[:n].copy_(up(pr, np.float32))
+            for dst, src in ((self.box_frame, fr), (self.box_class, cls), (self.box_group, ug)):
+                dst[:n].copy_(up(src, np.int32))
+        self.n_boxes.fill_(n)
+        return self
+
+    def step(self):
+        """Enqueues one batch on the current stream -- count, plan, fill, the gathers through slot_box, the draw,
+        fcn_prepare_inputs_infer and, with fov, the whole-image count, plan and fill -- and nothing else: no allocation, no host
+        read, no upload (capturable).  Returns the batch dict of InputBuilder.build_device() without 'kept', at batch size B1 -- an
+        empty slot holds the spare row's frustum over no rows -- plus slot_box (B1) int32 the box of each slot (D: empty), slot_frame,
+        slot_class, slot_group (B1) int32 its frame, class and group (spare_group: empty) and n_kept (1) the filled slots; the same
+        tensors every step.  check() reads the status words."""
+        L, dev, bld = _native.lib(), self.device, self.builder
+        B1, D, S, F, t, out = self.B1, self.D, self.S, self.F, self.t, self.out
+        p = lambda x: x.data_ptr()
+        pts, foff, P, V2C, R0, wh = self.frames
+        with torch.cuda.device(dev):
+            s = _native.current_stream(dev)
+            args = (p(pts), p(foff), F, self.ps, p(P), p(V2C), p(R0), p(wh), p(self.boxes2d), p(self.box_frame), D, S,
+                    1 if self.clip_boxes else 0, self.clip_distance, p(self.n_boxes))
+            _native.check(L.fcn_frustum_detect_count(*args, p(self.box2d), p(self.angle), p(self.seg_cnt), s), "fcn_frustum_detect_count")
+            _native.check(L.fcn_frustum_detect_plan(p(self.seg_cnt), p(self.box2d), p(self.box_frame), p(self.n_boxes),
+                                                    self.img_height_threshold, self.lidar_point_threshold, D, S, B1, self.capacity, F,
+                                                    p(self.slot_box), p(self.n_kept), p(self.seg_off), p(self.off), p(self.counts),
+                                                    p(self.status), s), "fcn_frustum_detect_plan")
+            _native.check(L.fcn_frustum_detect_fill(*args, p(self.seg_off), p(self.points), s), "fcn_frustum_detect_fill")
+            for src, dst in ((self.angle, t["fangle"]), (self.box2d, t["box2d"]), (self.box_prob.view(D + 1, 1), out["rgb_prob"]),
+                             (self.box_frame, self.slot_frame), (self.box_class, self.slot_class), (self.box_group, self.slot_group)):
+                torch.index_select(src, 0, self.slot_box, out=dst)
+            torch.index_select(P, 0, self.slot_frame, out=t["P"])
+            if "one_hot" in out:
+                torch.index_select(self.eye, 0, self.slot_class, out=out["one_hot"])
+            self.draws.draw(self.counts, bld.npoints, False, False, out=(t["choice"],) + self.scalars)
+            bld.launch_infer(t, out)
+            if self.fov:
+                fargs = (p(pts), p(foff), F, self.ps, p(P), p(V2C), p(R0), p(wh), p(self.fov_boxes), p(self.fov_frame), F, S, 0,
+                         self.clip_distance, p(self.fov_n))
+                _native.check(L.fcn_frustum_detect_count(*fargs, p(self.fov_box2d), p(self.fov_angle), p(self.fov_cnt), s),
+                              "fcn_frustum_detect_count")
+                _native.check(L.fcn_frustum_fov_plan(p(self.fov_cnt), F, S, int(pts.shape[0]), p(self.fov_seg_off), p(self.fov_off), s),
+                              "fcn_frustum_fov_plan")
+                _native.check(L.fcn_frustum_detect_fill(*fargs, p(self.fov_seg_off), p(self.fov_points), s), "fcn_frustum_detect_fill")
+        res = dict(out)
+        res.update(slot_box=self.slot_box, slot_frame=self.slot_frame, slot_class=self.slot_class, slot_group=self.slot_group,
+                   n_kept=self.n_kept)
+        return res
+
+    def check(self):
+        """Reads the status words of the plan and the draws (a synchronisation: not for a captured region); raises ValueError naming
+        the bits set since the last check() and clears them.  Bit 0 is the draws' own: an EMPTY slot has no row to draw from either,
+        so it is set by every step with fewer survivors than slots."""
+        words = (self.status, self.draws.status)
+        s = 0
+        for v in torch.cat(words).cpu().tolist():
+            s |= int(v)
+        if s:
+            for w in words:
+                w.zero_()
+            raise ValueError("FrameDetectSource: status %d -- %s" % (s, "; ".join(text for bit, text in STATUS_BITS if s & bit)))

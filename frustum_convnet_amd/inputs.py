@@ -283,6 +283,34 @@ class InputBuilder:
         out["kept"] = kept
         return out
 
+    def alloc_infer(self, B):
+        """Output tensors of launch_infer() for a batch of B frustums: the dict of build_device() without 'kept' -- point_cloud,
+        rot_angle, center_ref1..4, rgb_prob (B,1) and, with one_hot, one_hot (B, classes), both zeros for the caller to fill."""
+        dev, N = self.device, self.npoints
+        f32 = dict(dtype=torch.float32, device=dev)
+        out = {"point_cloud": torch.empty((B, 3, N), **f32), "rot_angle": torch.empty((B, 1), **f32)}
+        for s in range(4):
+            out["center_ref%d" % (s + 1)] = torch.empty((B, 3, self.L[s]), **f32)
+        out["rgb_prob"] = torch.zeros((B, 1), **f32)
+        if self.one_hot:
+            out["one_hot"] = torch.zeros((B, len(self.classes)), **f32)
+        return out
+
+    def launch_infer(self, t, out):
+        """ONE launch of fcn_prepare_inputs_infer on the current stream: device tensors `t` -- raw, off, choice, fangle, box2d, P,
+        B, pt_stride -- into the caller-owned `out` of alloc_infer(): no allocation, no host work besides the call (capturable into
+        a hipGraph).  rgb_prob / one_hot are the caller's to write.  Returns out."""
+        dev = self.device
+        desc = InpDesc(t["B"], self.npoints, t["pt_stride"], (ctypes.c_int32 * 4)(*self.L), (ctypes.c_double * 4)(*self.strides),
+                       self.max_depth, 0, 0)
+        refs = (ctypes.c_void_p * 4)(*[out["center_ref%d" % (s + 1)].data_ptr() for s in range(4)])
+        p = lambda x: x.data_ptr()
+        with torch.cuda.device(dev):
+            _native.check(_native.lib().fcn_prepare_inputs_infer(
+                ctypes.byref(desc), p(t["raw"]), p(t["off"]), p(t["choice"]), p(t["fangle"]), p(t["box2d"]), p(t["P"]),
+                p(out["point_cloud"]), refs, p(out["rot_angle"]), _native.current_stream(dev)), "fcn_prepare_inputs_infer")
+        return out
+
     def build_device_train(self, sel, P, types, draws=None, with_seg=True, out=None):
         """The first stage's TRAINING batch -- the dict of build(), same keys, shapes and dtypes -- straight from the device
         tensors of frustum.frustum_training_candidates: no point, label or corner leaves the device.  sel: its dict; P (F,3,4):

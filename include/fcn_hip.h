@@ -1091,6 +1091,52 @@ int fcn_refine_detect_plan(const int32_t *seg_cnt, const double *pred_size, cons
                            int B, int64_t capacity, int32_t *slot_unit, int32_t *n_kept, int64_t *seg_off, int64_t *off,
                            int64_t *counts, int32_t *status, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * The inference front with no host read between its launches (csrc/frustum_detect_plan.h; INTEGRATION.md "Capturable inference
+ * front" states the contract bit for bit, tests/frustum_detect_plan_ref.py restates it in numpy): count, plan, fill over a resident
+ * table of at most D 2-D detections -- none of them reads anything back, allocates or synchronises, so the sequence can be captured
+ * into a hipGraph.  Status bits of the plan (*status: one int32 on the device, OR-ed, never cleared here): bit 2 (4) rows dropped
+ * because the total exceeds the capacity; bit 8 (256) more surviving boxes than B1; bit 10 (1024) *n_boxes outside [0, D] (taken as
+ * 0 / D) or a box below *n_boxes whose frame is outside [0, F) (ignored, never dereferenced).  (Bit 0 is fcn_draw_batch's; fewer
+ * survivors than B1 is the normal case here and sets nothing.)
+ *
+ * fcn_frustum_detect_count / _fill: the selection of fcn_frustum_select_count / _fill -- the same fp64 predicate, the same box2d and
+ * frustum_angle, the same stored rows bit for bit, clip_boxes per launch -- without the read-back of box_frame and frame_off, and
+ * behind n_boxes (1) int32 on the device: box d is skipped silently when d >= *n_boxes or its frame is outside [0, F) -- its counts
+ * are 0, its rows of box2d / frustum_angle are NOT written, nothing of it is dereferenced or stored, the calls return 0.  "No frame
+ * is longer than S * fcn_frustum_select_seg() rows" is the caller's duty: rows beyond S segments would silently not be searched.
+ * Refusals as fcn_frustum_select_count / _fill, plus n_boxes == NULL: FCN_E_BADARG. */
+int fcn_frustum_detect_count(const float *frame_pts, const int64_t *frame_off, int F, int pt_stride, const double *P,
+                             const double *V2C, const double *R0, const double *img_wh, const double *boxes,
+                             const int32_t *box_frame, int D, int S, int clip_boxes, double clip_distance, const int32_t *n_boxes,
+                             double *box2d, double *frustum_angle, int32_t *seg_cnt, void *stream);
+int fcn_frustum_detect_fill(const float *frame_pts, const int64_t *frame_off, int F, int pt_stride, const double *P,
+                            const double *V2C, const double *R0, const double *img_wh, const double *boxes,
+                            const int32_t *box_frame, int D, int S, int clip_boxes, double clip_distance, const int32_t *n_boxes,
+                            const int64_t *seg_off, float *out_pts, void *stream);
+/* fcn_frustum_detect_plan: what the host does between count and fill and in InputBuilder.build_device, as one workgroup.  seg_cnt
+ * (D,S) int32 and box2d (D,4) fp64 from fcn_frustum_detect_count, box_frame (D), n_boxes (1).  With count_d = the sum of box d's
+ * positive segment counts, box d survives iff d < min(*n_boxes, D), its frame lies in [0, F), none of ymax - ymin <
+ * img_height_threshold, xmax - xmin < 1, (double)count_d < lidar_point_threshold holds (fp64 comparisons: a NaN difference does not
+ * skip, as in numpy) and count_d > 0.  The first B1 survivors in box order take the slots: slot_box (B1) int32, D for an empty slot;
+ * *n_kept.  seg_off (D*S+1) int64: the exclusive prefix sum of the slot-holding boxes' counts, every entry clamped to capacity (boxes
+ * without a slot get empty slices: the fill stores nothing for them).  off (B1+1) int64: a filled slot's first row, capacity (the
+ * spare row behind the buffer) for an empty one, off[B1] = the rows stored.  counts (B1) int64: the STORED rows per slot.  Box rows
+ * at or beyond *n_boxes and rows of boxes with a frame out of range are never read.  Every output is written on every call.
+ * NULL pointers, D < 0, S < 1, B1 < 1, capacity < 0, F < 0 or a NaN threshold: FCN_E_BADARG; D or B1 > 2048 or D * S > 65536
+ * (fcn_frustum_detect_plan_limits): FCN_E_LIMIT; nothing written. */
+int fcn_frustum_detect_plan(const int32_t *seg_cnt, const double *box2d, const int32_t *box_frame, const int32_t *n_boxes,
+                            double img_height_threshold, double lidar_point_threshold, int D, int S, int B1, int64_t capacity, int F,
+                            int32_t *slot_box, int32_t *n_kept, int64_t *seg_off, int64_t *off, int64_t *counts, int32_t *status,
+                            void *stream);
+int fcn_frustum_detect_plan_limits(int *max_d, int *max_segs);
+/* fcn_frustum_fov_plan: the plan of the whole-image selection (one box (0, 0, W, H) per frame, box_frame = 0..F-1, clip_boxes = 0,
+ * *n_boxes = F through fcn_frustum_detect_count / _fill): seg_cnt (F,S) -> seg_off (F*S+1) int64, the exclusive prefix sum of the
+ * positive counts, and fov_off (F+1) int64, every S-th entry of it (the frames' offsets).  No reject rule, no slots, no status.
+ * Entries are clamped to capacity; with capacity = the rows of the frame buffer nothing is ever cut, a subset of a frame being no
+ * longer than the frame.  NULL pointers, F < 0, S < 1 or capacity < 0: FCN_E_BADARG; F * S > 65536: FCN_E_LIMIT. */
+int fcn_frustum_fov_plan(const int32_t *seg_cnt, int F, int S, int64_t capacity, int64_t *seg_off, int64_t *fov_off, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
