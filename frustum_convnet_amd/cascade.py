@@ -25,7 +25,7 @@ import torch
 
 from . import _native
 from .detect import _need_cuda
-from .frustum import _frames
+from .frustum import _frames, check_status
 
 
 def refine_candidates(frame_points, frame_off, dets, cand_row, cand_frame, ratio=1.2):
@@ -391,14 +391,8 @@ class RefineTrainSource:
     def check(self):
         """Reads the status words of the plan and the three generators (a synchronisation: not for a captured region); raises
         ValueError naming the bits set since the last check() and clears them."""
-        words = (self.status, self.draws_pick.status, self.draws_jitter.status, self.draws_sample.status)
-        s = 0
-        for v in torch.cat(words).cpu().tolist():
-            s |= int(v)
-        if s:
-            for w in words:
-                w.zero_()
-            raise ValueError("RefineTrainSource: status %d -- %s" % (s, "; ".join(text for bit, text in STATUS_BITS if s & bit)))
+        check_status("RefineTrainSource", (self.status, self.draws_pick.status, self.draws_jitter.status, self.draws_sample.status),
+                     STATUS_BITS)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -567,14 +561,7 @@ class CascadeLink:
         """Reads the status words of the link and of its draws (a synchronisation: not for a captured region); raises ValueError
         naming the bits set since the last check() and clears them.  Bit 0 is the draws' own: an EMPTY slot has no row to draw
         from either, so it is set by every step with fewer survivors than slots."""
-        words = (self.status, self.draws.status)
-        s = 0
-        for v in torch.cat(words).cpu().tolist():
-            s |= int(v)
-        if s:
-            for w in words:
-                w.zero_()
-            raise ValueError("CascadeLink: status %d -- %s" % (s, "; ".join(text for bit, text in STATUS_BITS if s & bit)))
+        check_status("CascadeLink", (self.status, self.draws.status), STATUS_BITS)
 
 
 class FrameCascade:
@@ -622,14 +609,8 @@ class FrameCascade:
     def check(self):
         """check() of both parts in one: reads their status words (a synchronisation), raises ValueError naming the bits set since
         the last check() and clears them."""
-        words = (self.source.status, self.source.draws.status, self.link.status, self.link.draws.status)
-        s = 0
-        for v in torch.cat(words).cpu().tolist():
-            s |= int(v)
-        if s:
-            for w in words:
-                w.zero_()
-            raise ValueError("FrameCascade: status %d -- %s" % (s, "; ".join(text for bit, text in STATUS_BITS if s & bit)))
+        check_status("FrameCascade", (self.source.status, self.source.draws.status, self.link.status, self.link.draws.status),
+                     STATUS_BITS)
 
 
 class TwoStageDetector:

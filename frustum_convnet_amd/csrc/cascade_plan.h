@@ -6,14 +6,15 @@
 //   fcn_cascade_candidates     ONE workgroup: keep (G, top_k) / cnt (G) of fcn_rotate_nms_3d -> the first D kept rows, groups
 //                              ascending and keep order inside a group, with the frame, class and group of the frustum each row came
 //                              from (row / L2) and its score.  An order-preserving scan over the groups' valid entries
-//                              (fp_block_exscan, frustum_plan.h): no atomics on the data, nothing depends on scheduling.
+//                              (fp_block_exscan, slot_plan.h): no atomics on the data, nothing depends on scheduling.
 //   fcn_refine_detect_count    the count / fill of refine_select.h on the SEGMENTED (S, D) grid of seg_compact.h -- CdSelect is
 //   fcn_refine_detect_fill     RsSelect with WHOLE = false: the same geometry, predicate and header, the same row loop -- launched
 //                              without a read-back of the candidate lists: the kernels skip a candidate whose row or frame is out of
 //                              range (the filler rows of the table included); "no frame longer than S * FS_SEG rows" is the caller's
 //                              duty (checked once, where the frames are made resident);
-//   fcn_refine_detect_plan     rp_plan_kernel<true> (refine_plan.h) between the two, the positives being the counts themselves: the
-//                              reference's lidar_point_threshold = 1 (prepare_data_refine.py:739-741) as the reject rule.
+//   fcn_refine_detect_plan     the plan skeleton of slot_plan.h with RpPlan<true> (refine_plan.h) between the two, the positives
+//                              being the counts themselves: the reference's lidar_point_threshold = 1
+//                              (prepare_data_refine.py:739-741) as the reject rule.
 // Status bits (one int32 word, OR-ed, never cleared here): CD_ST_ROWS more kept rows than D; RP_ST_MANY more surviving candidates
 // than B; CD_ST_GROUP a group that overflowed the NMS (cnt = -1) or reports cnt > top_k, passed on to nobody; FP_ST_TRUNC, RP_ST_WIDE
 // and RP_ST_WIDTH as the training plan sets them (bit 0 is DeviceDraws').
@@ -50,9 +51,9 @@ __global__ __launch_bounds__(FP_T) void cd_candidates_kernel(CdCandArgs a)
 {
     __shared__ int64_t swave[FP_WAVES];
     const int tid = threadIdx.x, G = a.G, D = a.D;
-    // thread tid owns groups [tid * E, (tid + 1) * E): count their valid entries, scan, walk them again to write
-    const int E = (G + FP_T - 1) / FP_T;
-    const int g0 = tid * E < G ? tid * E : G, g1 = g0 + E < G ? g0 + E : G;
+    // the groups of this thread's run: count their valid entries, scan, walk them again to write
+    int g0, g1;
+    sl_run(G, tid, g0, g1);
     int64_t sum = 0;
     int st = 0;
     for (int g = g0; g < g1; ++g) {
@@ -104,9 +105,7 @@ extern "C" int fcn_cascade_candidates(const int32_t *keep, const int32_t *cnt, i
     a.G = G; a.top_k = top_k; a.L2 = L2; a.B1 = B1; a.R = R; a.D = D;
     a.crow = cand_row; a.cframe = cand_frame; a.cclass = cand_class; a.cgroup = cand_group; a.cscore = cand_score;
     a.n_cand = n_cand; a.status = status;
-    hipLaunchKernelGGL(cd_candidates_kernel, dim3(1), dim3(FP_T), 0, (hipStream_t)stream, a);
-    FCN_CHECK_LAUNCH();
-    return 0;
+    return sl_launch(cd_candidates_kernel, a, stream);
 }
 
 // ---- count / fill: RsSelect on the segmented grid
@@ -150,7 +149,7 @@ extern "C" int fcn_refine_detect_fill(const float *frame_pts, const int64_t *fra
     return sc_launch<CdSelect, true>(a, D, nullptr, 0, D, nullptr, F, (hipStream_t)stream, false);
 }
 
-// ---- the plan: the training plan's kernel with the counts as the positives
+// ---- the plan: the training plan's rule with the counts as the positives
 extern "C" int fcn_refine_detect_plan(const int32_t *seg_cnt, const double *pred_size, const double *stride, const int32_t *lpad,
                                       int D, int S, int B, int64_t capacity, int32_t *slot_unit, int32_t *n_kept, int64_t *seg_off,
                                       int64_t *off, int64_t *counts, int32_t *status, void *stream)

@@ -71,6 +71,30 @@ __device__ __forceinline__ double draw_u53(uint32_t hi, uint32_t lo)
     return (double)(hi >> 5) * 67108864.0 + (double)(lo >> 6);
 }
 
+// the counter's upper words and the key of stream `tag` at the device-resident step
+struct DrawKey {
+    uint32_t c2, c3, k0, k1;
+};
+
+__device__ __forceinline__ DrawKey draw_key(const int64_t *state, uint64_t seed, uint32_t tag)
+{
+    const uint64_t step = (uint64_t)state[0];
+    return {(uint32_t)step, ((uint32_t)(step >> 32) << 2) | tag, (uint32_t)seed, (uint32_t)(seed >> 32)};
+}
+
+// blocks blk0 .. blk0 + NB - 1 of row `row`: 2 * NB uniforms in [0, 1), u[2 i + j] = u53(words 2 j, 2 j + 1 of block blk0 + i) * 2^-53
+template <int NB> __device__ __forceinline__ void draw_uniforms(const DrawKey &k, uint32_t blk0, uint32_t row, double (&u)[2 * NB])
+{
+    const double scale = 1.0 / 9007199254740992.0;         // 2^-53
+#pragma unroll
+    for (int i = 0; i < NB; ++i) {
+        uint32_t w[4];
+        draw_philox(blk0 + (uint32_t)i, row, k.c2, k.c3, k.k0, k.k1, w);
+        u[2 * i] = draw_u53(w[0], w[1]) * scale;
+        u[2 * i + 1] = draw_u53(w[2], w[3]) * scale;
+    }
+}
+
 template <int DIGIT_BITS, int SORT_CAP, int MODE = DRAW_ROWS>
 __global__ __launch_bounds__(DRAW_T) void draw_batch_kernel(DrawArgs a)
 {
@@ -263,6 +287,15 @@ static __global__ void draw_advance_kernel(int64_t *state)
     if (blockIdx.x == 0 && threadIdx.x == 0) state[0] = state[0] + 1;
 }
 
+static inline int draw_advance(int advance, const int64_t *state, hipStream_t stream)
+{
+    if (advance) {
+        hipLaunchKernelGGL(draw_advance_kernel, dim3(1), dim3(64), 0, stream, (int64_t *)state);
+        FCN_CHECK_LAUNCH();
+    }
+    return 0;
+}
+
 template <int DIGIT_BITS, int SORT_CAP, int MODE = DRAW_ROWS>
 static inline int draw_batch_launch(const DrawArgs &a, hipStream_t stream, bool advance = true)
 {
@@ -270,11 +303,7 @@ static inline int draw_batch_launch(const DrawArgs &a, hipStream_t stream, bool 
     if (a.N > SORT_CAP) return FCN_E_LIMIT;
     hipLaunchKernelGGL((draw_batch_kernel<DIGIT_BITS, SORT_CAP, MODE>), dim3(a.B), dim3(DRAW_T), 0, stream, a);
     FCN_CHECK_LAUNCH();
-    if (advance) {
-        hipLaunchKernelGGL(draw_advance_kernel, dim3(1), dim3(64), 0, stream, (int64_t *)a.state);
-        FCN_CHECK_LAUNCH();
-    }
-    return 0;
+    return draw_advance(advance, a.state, stream);
 }
 
 #ifndef FCN_DRAWS_NO_ENTRY

@@ -8,27 +8,17 @@
 //   fcn_frustum_train_count    the count / fill of frustum_label.h (seg_compact.h with FlSelect), launched without a read-back: the
 //   fcn_frustum_train_fill     kernels skip a box whose frame is out of range; "no frame longer than S * FS_SEG rows" is the caller's
 //                              duty (checked once, where the frames are made resident);
-//   fcn_frustum_train_plan     ONE workgroup between the two: the reject rule per box, the first B survivors IN BOX ORDER -> slots,
-//                              the exclusive prefix sum of the slot-holding boxes' segment counts (int64, clamped to the capacity
-//                              of the point buffer) and the slots' row offsets.  Order-preserving scans, no atomics on the data:
-//                              the result does not depend on scheduling.
+//   fcn_frustum_train_plan     the plan skeleton of slot_plan.h with FpPlan between the two: a box is kept when its label box is at
+//                              least min_box_height high and it has a positive; off[slot] alone, no stored counts.
 // Status bits (one int32 word, OR-ed, never cleared here): FP_ST_FEW fewer than B survivors; FP_ST_TRUNC rows dropped because the
 // total exceeds the capacity; FP_ST_PERTURB a box without a valid draw in FP_ATTEMPTS attempts or with its frame out of range
 // (bit 0 is DeviceDraws': a sample nothing could be drawn from).
-// The plan is latency-bound (one workgroup, D * S int32): every thread owns a contiguous run of the flattened segments, sums it,
-// one scan over the 256 run totals (a wave scan by __shfl_up, then the four wave totals through LDS) gives its base, and it walks
-// the run again to write.
 #pragma once
 #include "draws.h"
 #include "frustum_label.h"
+#include "slot_plan.h"
 
-#define FP_T 256
-#define FP_WAVES (FP_T / 64)
 #define FP_ATTEMPTS 32                 // the retry bound of fcn_box2d_perturb (the reference loops for ever)
-#define FP_MAX_D 2048                  // boxes (and slots) of one plan: their slots live in LDS
-#define FP_MAX_SEGS 65536              // D * S of one plan: 256 segments per thread
-#define FP_ST_FEW 2                    // bit 1
-#define FP_ST_TRUNC 4                  // bit 2
 #define FP_ST_PERTURB 16               // bit 4
 
 struct FpPerturbArgs {
@@ -58,21 +48,15 @@ __global__ __launch_bounds__(FP_T) void fp_perturb_kernel(FpPerturbArgs a)
         const double W = a.wh[2 * (int64_t)f], H = a.wh[2 * (int64_t)f + 1];
         const double h = ymax - ymin, w = xmax - xmin;
         const double cx = (xmin + xmax) / 2.0, cy = (ymin + ymax) / 2.0;
-        const uint64_t step = (uint64_t)a.state[0];
-        const uint32_t c2 = (uint32_t)step, c3 = ((uint32_t)(step >> 32) << 2) | 3u;
-        const uint32_t k0 = (uint32_t)a.seed, k1 = (uint32_t)(a.seed >> 32);
-        const double scale = 1.0 / 9007199254740992.0;     // 2^-53
+        const DrawKey key = draw_key(a.state, a.seed, 3u);
         const double r = a.r;
         for (int t = 0; t < FP_ATTEMPTS && !done; ++t) {
-            uint32_t w0[4], w1[4];
-            draw_philox(2u * (uint32_t)t, (uint32_t)d, c2, c3, k0, k1, w0);
-            draw_philox(2u * (uint32_t)t + 1u, (uint32_t)d, c2, c3, k0, k1, w1);
-            const double u0 = draw_u53(w0[0], w0[1]) * scale, u1 = draw_u53(w0[2], w0[3]) * scale;
-            const double u2 = draw_u53(w1[0], w1[1]) * scale, u3 = draw_u53(w1[2], w1[3]) * scale;
-            const double cx2 = cx + (w * r) * (u0 * 2.0 - 1.0);
-            const double cy2 = cy + (h * r) * (u1 * 2.0 - 1.0);
-            const double h2 = h * ((1.0 + (u2 * 2.0) * r) - r);
-            const double w2 = w * ((1.0 + (u3 * 2.0) * r) - r);
+            double u[4];
+            draw_uniforms<2>(key, 2u * (uint32_t)t, (uint32_t)d, u);
+            const double cx2 = cx + (w * r) * (u[0] * 2.0 - 1.0);
+            const double cy2 = cy + (h * r) * (u[1] * 2.0 - 1.0);
+            const double h2 = h * ((1.0 + (u[2] * 2.0) * r) - r);
+            const double w2 = w * ((1.0 + (u[3] * 2.0) * r) - r);
             const double x0 = fmin(fmax(cx2 - w2 / 2.0, 0.0), W - 1.0), x1 = fmin(fmax(cx2 + w2 / 2.0, 0.0), W - 1.0);
             const double y0 = fmin(fmax(cy2 - h2 / 2.0, 0.0), H - 1.0), y1 = fmin(fmax(cy2 + h2 / 2.0, 0.0), H - 1.0);
             if (x0 < x1 && y0 < y1) {
@@ -88,96 +72,24 @@ __global__ __launch_bounds__(FP_T) void fp_perturb_kernel(FpPerturbArgs a)
 }
 
 struct FpPlanArgs {
-    const int32_t *scnt, *spos;        // (D,S)
+    SlArgs c;
+    const int32_t *spos;               // (D,S)
     const double *gt2d;                // (D,4)
     double min_h;
-    int D, S, B;
-    int64_t cap;
-    int32_t *slot_box;                 // (B)
-    int64_t *soff;                     // (D*S+1)
-    int64_t *off;                      // (B+1)
-    int32_t *n_kept;                   // (1)
-    int32_t *status;
 };
 
-// exclusive scan of one value per thread over the workgroup, in thread order; total: the sum, in every thread
-__device__ __forceinline__ int64_t fp_block_exscan(int64_t v, int64_t *swave, int tid, int64_t &total)
-{
-    const int lane = tid & 63, wave = tid >> 6;
-    int64_t inc = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int64_t t = __shfl_up(inc, o, 64);
-        if (lane >= o) inc += t;
-    }
-    __syncthreads();                                        // (the previous scan's readers are done with swave)
-    if (lane == 63) swave[wave] = inc;
-    __syncthreads();
-    int64_t base = 0;
-    total = 0;
-    for (int w = 0; w < FP_WAVES; ++w) {
-        if (w < wave) base += swave[w];
-        total += swave[w];
-    }
-    return base + (inc - v);
-}
-
-__global__ __launch_bounds__(FP_T) void fp_plan_kernel(FpPlanArgs a)
-{
-    __shared__ int32_t sslot[FP_MAX_D];                     // box -> its slot, -1 without one
-    __shared__ int64_t swave[FP_WAVES];
-    const int tid = threadIdx.x, D = a.D, S = a.S, B = a.B;
-    // ---- the reject rule and the slots: thread tid owns boxes [tid * EB, (tid + 1) * EB)
-    const int EB = (D + FP_T - 1) / FP_T;                   // <= FP_MAX_D / FP_T = 8
-    const int d0 = tid * EB < D ? tid * EB : D, d1 = d0 + EB < D ? d0 + EB : D;
-    unsigned keep = 0;
-    for (int d = d0; d < d1; ++d) {
-        int64_t pos = 0;
-        for (int s = 0; s < S; ++s) pos += a.spos[(int64_t)d * S + s];
+struct FpPlan {
+    using Args = FpPlanArgs;
+    static constexpr bool SLOTS = true, COUNTS = false, MANY = false;
+    __device__ static int live(const Args &a, int, int &) { return a.c.U; }
+    __device__ static bool keep(const Args &a, int d, int &)
+    {
+        const int64_t pos = sl_unit_sum(a.spos, d, a.c.S);
         const double *q = a.gt2d + (int64_t)d * 4;
-        if (!(q[3] - q[1] < a.min_h) && pos > 0) keep |= 1u << (d - d0);
+        return !(q[3] - q[1] < a.min_h) && pos > 0;
     }
-    int64_t survivors;
-    int64_t rank = fp_block_exscan((int64_t)__popc(keep), swave, tid, survivors);
-    for (int d = d0; d < d1; ++d) {
-        int slot = -1;
-        if (keep & (1u << (d - d0))) {
-            if (rank < B) { slot = (int)rank; a.slot_box[slot] = d; }
-            rank += 1;
-        }
-        sslot[d] = slot;
-    }
-    const int n = survivors < B ? (int)survivors : B;
-    for (int i = n + tid; i < B; i += FP_T) a.slot_box[i] = 0;
-    __syncthreads();
-    // ---- the segment offsets: thread tid owns the flattened segments [tid * E, (tid + 1) * E)
-    const int M = D * S;                                    // <= FP_MAX_SEGS
-    const int E = (M + FP_T - 1) / FP_T;
-    const int i0 = tid * E < M ? tid * E : M, i1 = i0 + E < M ? i0 + E : M;
-    int64_t sum = 0;
-    for (int i = i0; i < i1; ++i) {
-        const int c = a.scnt[i];
-        if (sslot[i / S] >= 0 && c > 0) sum += c;
-    }
-    int64_t total;
-    int64_t run = fp_block_exscan(sum, swave, tid, total);
-    for (int i = i0; i < i1; ++i) {
-        const int slot = sslot[i / S];
-        const int64_t at = run < a.cap ? run : a.cap;
-        a.soff[i] = at;
-        if (slot >= 0 && i % S == 0) a.off[slot] = at;
-        const int c = a.scnt[i];
-        if (slot >= 0 && c > 0) run += c;
-    }
-    const int64_t end = total < a.cap ? total : a.cap;
-    for (int i = n + tid; i <= B; i += FP_T) a.off[i] = end;
-    if (tid == 0) {
-        a.soff[M] = end;
-        a.n_kept[0] = n;
-        const int st = (survivors < B ? FP_ST_FEW : 0) | (total > a.cap ? FP_ST_TRUNC : 0);
-        if (st) atomicOr(a.status, st);
-    }
-}
+    __device__ static int filler(const Args &) { return 0; }   // an empty slot repeats box 0's labels over no rows
+};
 
 extern "C" int fcn_box2d_perturb_limits(int *attempts)
 {
@@ -207,11 +119,7 @@ extern "C" int fcn_box2d_perturb(const double *boxes, const int32_t *box_frame, 
         hipLaunchKernelGGL(fp_perturb_kernel, dim3((D + FP_T - 1) / FP_T), dim3(FP_T), 0, (hipStream_t)stream, a);
         FCN_CHECK_LAUNCH();
     }
-    if (advance) {                                          // state[0] + 1, in stream order behind every lane's read
-        hipLaunchKernelGGL(draw_advance_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (int64_t *)state);
-        FCN_CHECK_LAUNCH();
-    }
-    return 0;
+    return draw_advance(advance, state, (hipStream_t)stream);
 }
 
 extern "C" int fcn_frustum_train_count(const float *frame_pts, const int64_t *frame_off, int F, int pt_stride, const double *P,
@@ -239,12 +147,9 @@ extern "C" int fcn_frustum_train_plan(const int32_t *seg_cnt, const int32_t *seg
                                       int32_t *n_kept, int32_t *status, void *stream)
 {
     if (!seg_cnt || !seg_pos || !gt_box2d || !slot_box || !seg_off || !off || !n_kept || !status) return FCN_E_BADARG;
-    if (D < 0 || S < 1 || B < 1 || capacity < 0) return FCN_E_BADARG;
-    if (D > FP_MAX_D || B > FP_MAX_D || (int64_t)D * S > FP_MAX_SEGS) return FCN_E_LIMIT;
+    FCN_TRY(sl_sizes(D, S, B, capacity));
     FpPlanArgs a;
-    a.scnt = seg_cnt; a.spos = seg_pos; a.gt2d = gt_box2d; a.min_h = min_box_height; a.D = D; a.S = S; a.B = B; a.cap = capacity;
-    a.slot_box = slot_box; a.soff = seg_off; a.off = off; a.n_kept = n_kept; a.status = status;
-    hipLaunchKernelGGL(fp_plan_kernel, dim3(1), dim3(FP_T), 0, (hipStream_t)stream, a);
-    FCN_CHECK_LAUNCH();
-    return 0;
+    a.c = SlArgs{seg_cnt, D, S, B, capacity, slot_box, n_kept, seg_off, off, nullptr, status};
+    a.spos = seg_pos; a.gt2d = gt_box2d; a.min_h = min_box_height;
+    return sl_launch(sl_plan_kernel<FpPlan>, a, stream);
 }

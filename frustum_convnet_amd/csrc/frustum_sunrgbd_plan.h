@@ -8,24 +8,22 @@
 //   fcn_frustum_sunrgbd_train_count  the labelled count / fill of frustum_sunrgbd.h (seg_compact.h with SrSelect<true>), launched without
 //   fcn_frustum_sunrgbd_train_fill   a read-back: the kernels skip a box whose frame is out of range; "no frame longer than
 //                                    S * FS_SEG rows" is the caller's duty (checked once, where the frames are made resident);
-//   fcn_frustum_sunrgbd_train_plan   ONE workgroup between the two: the full-positive bar per box (pre-kept), the exclusive prefix sum
-//                                    of the pre-kept boxes' segment counts (int64, clamped to the capacity of the point buffer), the
-//                                    rows of each box that fit under the clamp (cnt_stored) and the offsets of the subsample table;
+//   fcn_frustum_sunrgbd_train_plan   ONE workgroup between the two, built from the steps of slot_plan.h: the full-positive bar per box
+//                                    (pre-kept, no slots yet), sl_offsets over the pre-kept boxes' segment counts, the rows of each
+//                                    box that fit under the clamp (cnt_stored) and the offsets of the subsample table;
 //   fcn_frustum_subsample_draw       draw_batch_kernel of draws.h in its DRAW_SUBSAMPLE form: for every box of more than `cap` STORED
 //                                    rows the row-d choice of fcn_draw_batch at N = cap, n = cnt_stored[d] (the whole-row LDS sort and
 //                                    the radix select are that kernel's: there is one selection);
-//   fcn_frustum_sunrgbd_train_slots  ONE workgroup behind fcn_frustum_subset_pos: the post-subsample bar, the first B survivors IN BOX
-//                                    ORDER -> slots, and per slot what fcn_draw_batch_sliced and fcn_prepare_inputs_sunrgbd read;
+//   fcn_frustum_sunrgbd_train_slots  ONE workgroup behind fcn_frustum_subset_pos: sl_assign under the post-subsample bar, and per
+//                                    slot what fcn_draw_batch_sliced and fcn_prepare_inputs_sunrgbd read;
 //   fcn_draw_batch_sliced            draw_batch_kernel in its DRAW_SLICED form: fcn_draw_batch with a (start, length) pair per row in
 //                                    place of the packed sub_off.
 // From the plan on every count is cnt_stored: no index ever points at a row that was not stored.  Order-preserving scans, no atomics
 // on the data: the result does not depend on scheduling.  Status bits (one int32 word, OR-ed, never cleared here): FP_ST_FEW fewer
 // than B survivors; FP_ST_TRUNC rows dropped because the total exceeds the capacity (bit 0 is the draws'; bit 4 is never set here).
-// Both one-workgroup kernels are latency-bound and built like fp_plan_kernel: every thread owns a contiguous run of boxes (or of the
-// flattened segments), one scan over the 256 run totals gives its base, and it walks the run again to write.
 #pragma once
 #include "draws.h"
-#include "frustum_plan.h"
+#include "slot_plan.h"
 #include "frustum_sunrgbd.h"
 
 struct SpPerturbArgs {
@@ -47,20 +45,13 @@ __global__ __launch_bounds__(FP_T) void sp_perturb_kernel(SpPerturbArgs a)
     const double xmin = q[0], ymin = q[1], xmax = q[2], ymax = q[3];
     const double h = ymax - ymin, w = xmax - xmin;
     const double cx = (xmin + xmax) / 2.0, cy = (ymin + ymax) / 2.0;
-    const uint64_t step = (uint64_t)a.state[0];
-    const uint32_t c2 = (uint32_t)step, c3 = ((uint32_t)(step >> 32) << 2) | 3u;
-    const uint32_t k0 = (uint32_t)a.seed, k1 = (uint32_t)(a.seed >> 32);
-    const double scale = 1.0 / 9007199254740992.0;         // 2^-53
     const double r = a.r;
-    uint32_t w0[4], w1[4];
-    draw_philox(0u, (uint32_t)d, c2, c3, k0, k1, w0);
-    draw_philox(1u, (uint32_t)d, c2, c3, k0, k1, w1);
-    const double u0 = draw_u53(w0[0], w0[1]) * scale, u1 = draw_u53(w0[2], w0[3]) * scale;
-    const double u2 = draw_u53(w1[0], w1[1]) * scale, u3 = draw_u53(w1[2], w1[3]) * scale;
-    const double cx2 = cx + (w * r) * (u0 * 2.0 - 1.0);
-    const double cy2 = cy + (h * r) * (u1 * 2.0 - 1.0);
-    const double h2 = h * ((1.0 + (u2 * 2.0) * r) - r);
-    const double w2 = w * ((1.0 + (u3 * 2.0) * r) - r);
+    double u[4];
+    draw_uniforms<2>(draw_key(a.state, a.seed, 3u), 0u, (uint32_t)d, u);
+    const double cx2 = cx + (w * r) * (u[0] * 2.0 - 1.0);
+    const double cy2 = cy + (h * r) * (u[1] * 2.0 - 1.0);
+    const double h2 = h * ((1.0 + (u[2] * 2.0) * r) - r);
+    const double w2 = w * ((1.0 + (u[3] * 2.0) * r) - r);
     double *o = a.out + (int64_t)d * 4;
     o[0] = cx2 - w2 / 2.0; o[1] = cy2 - h2 / 2.0; o[2] = cx2 + w2 / 2.0; o[3] = cy2 + h2 / 2.0;
 }
@@ -78,41 +69,18 @@ struct SpPlanArgs {
 
 __global__ __launch_bounds__(FP_T) void sp_plan_kernel(SpPlanArgs a)
 {
-    __shared__ int32_t skeep[FP_MAX_D];                     // box -> pre-kept
+    __shared__ int32_t skeep[FP_MAX_D];                     // box -> pre-kept: 0, else -1 (sl_offsets' "slot")
     __shared__ int64_t sstart[FP_MAX_D + 1];                // box -> its first row (clamped); [D] the clamped total
     __shared__ int64_t swave[FP_WAVES];
-    const int tid = threadIdx.x, D = a.D, S = a.S;
-    // ---- the full-positive bar: thread tid owns boxes [tid * EB, (tid + 1) * EB)
-    const int EB = (D + FP_T - 1) / FP_T;                   // <= FP_MAX_D / FP_T = 8
-    const int d0 = tid * EB < D ? tid * EB : D, d1 = d0 + EB < D ? d0 + EB : D;
-    for (int d = d0; d < d1; ++d) {
-        int64_t pos = 0;
-        for (int s = 0; s < S; ++s) pos += a.spos[(int64_t)d * S + s];
-        skeep[d] = pos >= a.min_pos ? 1 : 0;
-    }
+    const int tid = threadIdx.x, D = a.D;
+    int d0, d1;
+    sl_run(D, tid, d0, d1);
+    for (int d = d0; d < d1; ++d) skeep[d] = sl_unit_sum(a.spos, d, a.S) >= a.min_pos ? 0 : -1;     // the full-positive bar
     __syncthreads();
-    // ---- the segment offsets: thread tid owns the flattened segments [tid * E, (tid + 1) * E)
-    const int M = D * S;                                    // <= FP_MAX_SEGS
-    const int E = (M + FP_T - 1) / FP_T;
-    const int i0 = tid * E < M ? tid * E : M, i1 = i0 + E < M ? i0 + E : M;
-    int64_t sum = 0;
-    for (int i = i0; i < i1; ++i) {
-        const int c = a.scnt[i];
-        if (skeep[i / S] && c > 0) sum += c;
-    }
-    int64_t total;
-    int64_t run = fp_block_exscan(sum, swave, tid, total);
-    for (int i = i0; i < i1; ++i) {
-        const int64_t at = run < a.capacity ? run : a.capacity;
-        a.soff[i] = at;
-        if (i % S == 0) { a.row0[i / S] = at; sstart[i / S] = at; }
-        const int c = a.scnt[i];
-        if (skeep[i / S] && c > 0) run += c;
-    }
-    const int64_t end = total < a.capacity ? total : a.capacity;
+    const int64_t total = sl_offsets(a.scnt, D, a.S, a.capacity, a.soff, swave, tid, [&](int d) { return (int)skeep[d]; },
+                                     [&](int d, int, int64_t at) { a.row0[d] = at; sstart[d] = at; }, [](int, int, int64_t) {});
     if (tid == 0) {
-        a.soff[M] = end;
-        sstart[D] = end;
+        sstart[D] = total < a.capacity ? total : a.capacity;
         if (total > a.capacity) atomicOr(a.status, FP_ST_TRUNC);
     }
     __syncthreads();
@@ -152,37 +120,25 @@ struct SpSlotsArgs {
 __global__ __launch_bounds__(FP_T) void sp_slots_kernel(SpSlotsArgs a)
 {
     __shared__ int64_t swave[FP_WAVES];
-    const int tid = threadIdx.x, D = a.D, S = a.S, B = a.B;
-    const int EB = (D + FP_T - 1) / FP_T;
-    const int d0 = tid * EB < D ? tid * EB : D, d1 = d0 + EB < D ? d0 + EB : D;
-    unsigned keep = 0;
-    for (int d = d0; d < d1; ++d) {
-        int64_t full = 0;
-        for (int s = 0; s < S; ++s) full += a.spos[(int64_t)d * S + s];
-        if (full >= a.min_pos && a.pos[d] >= a.min_pos) keep |= 1u << (d - d0);
-    }
+    const int tid = threadIdx.x;
     int64_t survivors;
-    int64_t rank = fp_block_exscan((int64_t)__popc(keep), swave, tid, survivors);
-    for (int d = d0; d < d1; ++d) {
-        if (!(keep & (1u << (d - d0)))) continue;
-        if (rank < B) {
-            const int i = (int)rank;
-            const int64_t s0 = a.sub_off[d], s1 = a.sub_off[d + 1];
-            a.slot_box[i] = d;
-            a.off[i] = a.row0[d];
-            a.counts[i] = a.cnt_stored[d];
-            a.sub_start[i] = s1 > s0 ? s0 : 0;
-            a.sub_len[i] = s1 > s0 ? (int32_t)(s1 - s0) : 0;
-        }
-        rank += 1;
-    }
-    const int n = survivors < B ? (int)survivors : B;
-    for (int i = n + tid; i < B; i += FP_T) {               // an empty slot: box 0's labels over no rows, reading the spare row
-        a.slot_box[i] = 0; a.off[i] = a.capacity; a.counts[i] = 0; a.sub_start[i] = 0; a.sub_len[i] = 0;
-    }
+    const int n = sl_assign(a.D, a.B, swave, tid, survivors,
+                            [&](int d) { return sl_unit_sum(a.spos, d, a.S) >= a.min_pos && a.pos[d] >= a.min_pos; },
+                            [&](int d, int i) {
+                                if (i < 0) return;
+                                const int64_t s0 = a.sub_off[d], s1 = a.sub_off[d + 1];
+                                a.slot_box[i] = d;
+                                a.off[i] = a.row0[d];
+                                a.counts[i] = a.cnt_stored[d];
+                                a.sub_start[i] = s1 > s0 ? s0 : 0;
+                                a.sub_len[i] = s1 > s0 ? (int32_t)(s1 - s0) : 0;
+                            },
+                            [&](int i) {                    // an empty slot: box 0's labels over no rows, reading the spare row
+                                a.slot_box[i] = 0; a.off[i] = a.capacity; a.counts[i] = 0; a.sub_start[i] = 0; a.sub_len[i] = 0;
+                            });
     if (tid == 0) {
         a.n_kept[0] = n;
-        if (survivors < B) atomicOr(a.status, FP_ST_FEW);
+        if (survivors < a.B) atomicOr(a.status, FP_ST_FEW);
     }
 }
 
@@ -197,11 +153,7 @@ extern "C" int fcn_box2d_perturb_sunrgbd(const double *boxes, int D, double shif
         hipLaunchKernelGGL(sp_perturb_kernel, dim3((D + FP_T - 1) / FP_T), dim3(FP_T), 0, (hipStream_t)stream, a);
         FCN_CHECK_LAUNCH();
     }
-    if (advance) {                                          // state[0] + 1, in stream order behind every lane's read
-        hipLaunchKernelGGL(draw_advance_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (int64_t *)state);
-        FCN_CHECK_LAUNCH();
-    }
-    return 0;
+    return draw_advance(advance, state, (hipStream_t)stream);
 }
 
 extern "C" int fcn_frustum_sunrgbd_train_count(const float *frame_pts, const int64_t *frame_off, int F, int pt_stride,
@@ -227,14 +179,12 @@ extern "C" int fcn_frustum_sunrgbd_train_plan(const int32_t *seg_cnt, const int3
                                               int64_t *sub_off, int32_t *status, void *stream)
 {
     if (!seg_cnt || !seg_pos || !seg_off || !row0 || !cnt_stored || !sub_off || !status) return FCN_E_BADARG;
-    if (D < 0 || S < 1 || cap < 1 || capacity < 0) return FCN_E_BADARG;
-    if (D > FP_MAX_D || (int64_t)D * S > FP_MAX_SEGS) return FCN_E_LIMIT;
+    if (cap < 1) return FCN_E_BADARG;
+    FCN_TRY(sl_sizes(D, S, 1, capacity));
     SpPlanArgs a;
     a.scnt = seg_cnt; a.spos = seg_pos; a.min_pos = min_positives; a.cap = cap; a.D = D; a.S = S; a.capacity = capacity;
     a.soff = seg_off; a.row0 = row0; a.cnt_stored = cnt_stored; a.sub_off = sub_off; a.status = status;
-    hipLaunchKernelGGL(sp_plan_kernel, dim3(1), dim3(FP_T), 0, (hipStream_t)stream, a);
-    FCN_CHECK_LAUNCH();
-    return 0;
+    return sl_launch(sp_plan_kernel, a, stream);
 }
 
 extern "C" int fcn_frustum_subsample_draw(const int32_t *cnt_stored, const int64_t *sub_off, int D, int cap, uint64_t seed,
@@ -250,11 +200,7 @@ extern "C" int fcn_frustum_subsample_draw(const int32_t *cnt_stored, const int64
         a.cnt32 = cnt_stored; a.out_off = sub_off;
         FCN_TRY((draw_batch_launch<DRAW_DIGIT_BITS, DRAW_SORT_CAP, DRAW_SUBSAMPLE>(a, (hipStream_t)stream, false)));
     }
-    if (advance) {
-        hipLaunchKernelGGL(draw_advance_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, state);
-        FCN_CHECK_LAUNCH();
-    }
-    return 0;
+    return draw_advance(advance, state, (hipStream_t)stream);
 }
 
 extern "C" int fcn_frustum_sunrgbd_train_slots(const int32_t *seg_pos, const int32_t *pos, const int64_t *row0,
@@ -265,15 +211,12 @@ extern "C" int fcn_frustum_sunrgbd_train_slots(const int32_t *seg_pos, const int
     if (!seg_pos || !pos || !row0 || !cnt_stored || !sub_off || !slot_box || !n_kept || !off || !counts || !sub_start || !sub_len ||
         !status)
         return FCN_E_BADARG;
-    if (D < 0 || S < 1 || B < 1 || capacity < 0) return FCN_E_BADARG;
-    if (D > FP_MAX_D || B > FP_MAX_D || (int64_t)D * S > FP_MAX_SEGS) return FCN_E_LIMIT;
+    FCN_TRY(sl_sizes(D, S, B, capacity));
     SpSlotsArgs a;
     a.spos = seg_pos; a.pos = pos; a.row0 = row0; a.cnt_stored = cnt_stored; a.sub_off = sub_off; a.min_pos = min_positives;
     a.D = D; a.S = S; a.B = B; a.capacity = capacity; a.slot_box = slot_box; a.n_kept = n_kept; a.off = off; a.counts = counts;
     a.sub_start = sub_start; a.sub_len = sub_len; a.status = status;
-    hipLaunchKernelGGL(sp_slots_kernel, dim3(1), dim3(FP_T), 0, (hipStream_t)stream, a);
-    FCN_CHECK_LAUNCH();
-    return 0;
+    return sl_launch(sp_slots_kernel, a, stream);
 }
 
 extern "C" int fcn_draw_batch_sliced(const fcn_draw_desc *d, const int64_t *counts, const int32_t *sub, const int64_t *sub_start,

@@ -409,6 +409,18 @@ def sunrgbd_training_candidates(frame_points, frame_off, K, Rtilt, boxes2d, box_
 
 # ------------------------------------------------------------------------------------------------
 # The KITTI first stage's training input as ONE capturable sequence of launches (csrc/frustum_plan.h)
+def check_status(who, words, bits):
+    """The check() of every capturable source: reads the status words (a synchronisation); where a bit is set, clears the words and
+    raises ValueError naming who and the texts of the set bits (bits: a STATUS_BITS table)."""
+    s = 0
+    for v in torch.cat(words).cpu().tolist():
+        s |= int(v)
+    if s:
+        for w in words:
+            w.zero_()
+        raise ValueError("%s: status %d -- %s" % (who, s, "; ".join(text for bit, text in bits if s & bit)))
+
+
 STATUS_BITS = ((1, "bit 0: a slot had no row to draw from (its choice row is zeros)"),
                (2, "bit 1: fewer boxes survived than the batch has slots (the empty slots repeat box 0's labels over no rows)"),
                (4, "bit 2: the selected rows exceed the capacity of the point buffer (the overflow was dropped)"),
@@ -587,14 +599,8 @@ class FrameTrainSource:
     def check(self):
         """Reads the status words of the plan, the perturbation and the three generators (a synchronisation: not for a captured
         region); raises ValueError naming the bits set since the last check() and clears them."""
-        words = (self.status, self.draws_pick.status, self.draws_box.status, self.draws_sample.status)
-        s = 0
-        for v in torch.cat(words).cpu().tolist():
-            s |= int(v)
-        if s:
-            for w in words:
-                w.zero_()
-            raise ValueError("FrameTrainSource: status %d -- %s" % (s, "; ".join(text for bit, text in STATUS_BITS if s & bit)))
+        check_status("FrameTrainSource", (self.status, self.draws_pick.status, self.draws_box.status, self.draws_sample.status),
+                     STATUS_BITS)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -809,14 +815,8 @@ class SunrgbdTrainSource:
     def check(self):
         """Reads the status words of the plan, the slots and the four generators (a synchronisation: not for a captured region);
         raises ValueError naming the bits set since the last check() and clears them."""
-        words = (self.status, self.draws_pick.status, self.draws_box.status, self.draws_sample.status, self.draws_sub.status)
-        s = 0
-        for v in torch.cat(words).cpu().tolist():
-            s |= int(v)
-        if s:
-            for w in words:
-                w.zero_()
-            raise ValueError("SunrgbdTrainSource: status %d -- %s" % (s, "; ".join(text for bit, text in STATUS_BITS if s & bit)))
+        check_status("SunrgbdTrainSource", (self.status, self.draws_pick.status, self.draws_box.status, self.draws_sample.status,
+                                            self.draws_sub.status), STATUS_BITS)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -1005,11 +1005,4 @@ class FrameDetectSource:
         """Reads the status words of the plan and the draws (a synchronisation: not for a captured region); raises ValueError naming
         the bits set since the last check() and clears them.  Bit 0 is the draws' own: an EMPTY slot has no row to draw from either,
         so it is set by every step with fewer survivors than slots."""
-        words = (self.status, self.draws.status)
-        s = 0
-        for v in torch.cat(words).cpu().tolist():
-            s |= int(v)
-        if s:
-            for w in words:
-                w.zero_()
-            raise ValueError("FrameDetectSource: status %d -- %s" % (s, "; ".join(text for bit, text in STATUS_BITS if s & bit)))
+        check_status("FrameDetectSource", (self.status, self.draws.status), STATUS_BITS)

@@ -22,6 +22,7 @@ CASES += [
     ("test_plan_equals_the_restatement", (4,)),
     ("test_plan_equals_the_restatement", (10,)),
     ("test_plan_equals_the_restatement", (12,)),
+    *[("test_plan_where_a_threads_run_goes_from_one_candidate_to_two", (D, S)) for D in (255, 256, 257) for S in (1, 3)],
     ("test_plan_at_its_smallest_and_at_its_limits", ()),
     ("test_plan_widths", ()),
     ("test_count_plan_fill_stays_within_capacity_plus_one_rows", ()),

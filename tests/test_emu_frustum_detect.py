@@ -17,6 +17,7 @@ CASES = [("test_plan_box_count_frames_and_slots", (c,))
                    "B1_plus_1", "no_survivor")]
 CASES += [("test_plan_knife_edges", ())]
 CASES += [("test_plan_capacity_and_segments", (S,)) for S in (1, 3)]
+CASES += [("test_plans_where_a_threads_run_goes_from_one_box_to_two", (D, S)) for D in (255, 256, 257) for S in (1, 3)]
 CASES += [("test_plan_at_its_limits_and_refusals", ())]
 CASES += [("test_selection_equals_the_reading_selection_byte_for_byte", (stride, clip)) for stride in (4, 5) for clip in (True, False)]
 CASES += [

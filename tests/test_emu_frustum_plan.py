@@ -22,6 +22,7 @@ CASES = [
     ("test_plan_equals_the_restatement", (4,)),
     ("test_plan_equals_the_restatement", (12,)),
     ("test_plan_at_its_smallest_and_over_many_boxes", ()),
+    *[("test_plan_where_a_threads_run_goes_from_one_box_to_two", (D, S)) for D in (255, 256, 257) for S in (1, 3)],
     ("test_no_read_count_and_fill_equal_the_label_entries_bit_for_bit", (4,)),
     ("test_no_read_count_and_fill_equal_the_label_entries_bit_for_bit", (5,)),
     ("test_step_equals_the_existing_path_on_the_same_boxes", (4, 4)),

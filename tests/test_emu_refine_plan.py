@@ -17,6 +17,7 @@ CASES += [
     ("test_plan_equals_the_restatement", (4,)),
     ("test_plan_equals_the_restatement", (10,)),
     ("test_plan_equals_the_restatement", (12,)),
+    *[("test_plan_where_a_threads_run_goes_from_one_unit_to_two", (U, S)) for U in (255, 256, 257) for S in (1, 3)],
     ("test_plan_at_its_smallest_and_at_its_limits", ()),
     ("test_plan_widths", ()),
     ("test_no_read_entries_equal_the_reading_entries_bit_for_bit", (4,)),

@@ -23,6 +23,7 @@ CASES = [
     ("test_plan_subsample_and_slots_equal_the_restatement", (4,)),
     ("test_plan_subsample_and_slots_equal_the_restatement", (12,)),
     ("test_plan_subsample_and_slots_at_their_smallest_and_over_many_boxes", ()),
+    *[("test_plan_and_slots_where_a_threads_run_goes_from_one_box_to_two", (D, S)) for D in (255, 256, 257) for S in (1, 3)],
     ("test_subsample_of_more_rows_than_the_draws_sort_whole", ()),
     ("test_sliced_draw_equals_the_packed_draw_and_reads_the_right_slice", ()),
     ("test_step_equals_the_existing_path_on_the_same_boxes", (12, 3, None, True)),

@@ -287,6 +287,20 @@ def test_plan_equals_the_restatement(B):
     assert n == 0 and st == 0 and not seg_off.any() and off.tolist() == [1000] * B + [0] and (slot_unit == 12).all()
 
 
+@pytest.mark.parametrize("S", [1, 3])
+@pytest.mark.parametrize("D", [255, 256, 257])
+def test_plan_where_a_threads_run_goes_from_one_candidate_to_two(D, S):
+    """The run-per-thread split is csrc/slot_plan.h's, shared by every plan: over 256 threads, 255 and 256 candidates are runs of
+    one (the last thread's empty, then not), 257 candidates are runs of two with threads 129.. owning nothing.  B = D, some
+    candidates without a row, a capacity one row short of the total."""
+    rs = np.random.RandomState(4 * D + S)
+    cnt = rs.randint(0, 900, (D, S)) * (rs.uniform(size=(D, 1)) < 0.7)
+    psz = np.stack([rs.uniform(3, 5, D), rs.uniform(0.5, 2.5, D), rs.uniform(1, 2, D)], 1)
+    total = int(cnt.sum())
+    slot_unit, n, seg_off, off, counts, st = _plan_equals(cnt, psz, D, total - 1)
+    assert 0 < n < D and st == R.ST_TRUNC and seg_off[-1] == total - 1 and counts.sum() == total - 1
+
+
 def test_plan_at_its_smallest_and_at_its_limits():
     assert _plan_equals([[7]], [[4.0, 1.6, 1.5]], 1, 100)[3].tolist() == [0, 7]        # D = B = S = 1
     assert _plan_equals([[0]], [[4.0, 1.6, 1.5]], 1, 100)[5] == 0

@@ -132,6 +132,32 @@ def test_plan_capacity_and_segments(S):
     assert _plan_equals(cnt, box, frame, D, 8, 0, 4)[2].any() == False
 
 
+@pytest.mark.parametrize("S", [1, 3])
+@pytest.mark.parametrize("D", [255, 256, 257])
+def test_plans_where_a_threads_run_goes_from_one_box_to_two(D, S):
+    """The run-per-thread split is csrc/slot_plan.h's, shared by every plan: over 256 threads, 255 and 256 boxes are runs of one
+    (the last thread's empty, then not), 257 boxes are runs of two with threads 129.. owning nothing.  B1 = D, some boxes without
+    a row or too low, a capacity one row short of the total; then the FOV form over as many frames."""
+    from frustum_convnet_amd import _native
+    rs = np.random.RandomState(4 * D + S)
+    cnt = rs.randint(0, 900, (D, S)) * (rs.uniform(size=(D, 1)) < 0.8)
+    box = np.tile(np.asarray([[10.0, 20.0, 110.0, 90.0]]), (D, 1))
+    box[::7, 3] = 22.0
+    frame = rs.randint(0, 4, D)
+    total = int(R.plan(cnt, box, frame, D, 5.0, 1.0, D, 1 << 40, 4)[2][-1])
+    slot_box, n, seg_off, off, counts, st = _plan_equals(cnt, box, frame, D, D, total - 1, 4)
+    assert 0 < n < D and st == R.ST_TRUNC and seg_off[-1] == total - 1 and counts.sum() == total - 1
+    seg_off, sbuf = _guarded((D * S + 1,), torch.int64, -7)
+    fov_off, fbuf = _guarded((D + 1,), torch.int64, -7)
+    cnt_d = _dev(cnt.astype(np.int32))
+    total = int(cnt.sum())
+    assert _native.lib().fcn_frustum_fov_plan(_p(cnt_d), D, S, total - 1, _p(seg_off), _p(fov_off), _native.current_stream()) == 0
+    torch.cuda.synchronize()
+    ws, wf = R.fov_plan(cnt, total - 1)
+    assert _intact(sbuf, -7) and _intact(fbuf, -7) and seg_off.cpu().numpy().tobytes() == ws.tobytes() and fov_off.cpu().numpy().tobytes() == wf.tobytes()
+    assert wf[-1] == total - 1
+
+
 def test_plan_at_its_limits_and_refusals():
     from frustum_convnet_amd import _native, frustum
     L, s = _native.lib(), _native.current_stream()

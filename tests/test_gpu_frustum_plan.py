@@ -261,6 +261,21 @@ def test_plan_at_its_smallest_and_over_many_boxes():
     _plan_equals(cnt, pos, gt2d, 25.0, D, 1 << 40)
 
 
+@pytest.mark.parametrize("S", [1, 3])
+@pytest.mark.parametrize("D", [255, 256, 257])
+def test_plan_where_a_threads_run_goes_from_one_box_to_two(D, S):
+    """The run-per-thread split is csrc/slot_plan.h's, shared by every plan: over 256 threads, 255 and 256 boxes are runs of one
+    (the last thread's empty, then not), 257 boxes are runs of two with threads 129.. owning nothing.  B = D, some boxes rejected,
+    a capacity one row short of the total."""
+    rs = np.random.RandomState(4 * D + S)
+    cnt = rs.randint(0, 900, (D, S))
+    pos = np.minimum(cnt, rs.randint(0, 40, (D, S))) * (rs.uniform(size=(D, 1)) < 0.7)
+    gt2d = np.stack([np.zeros(D), np.zeros(D), np.full(D, 50.0), rs.uniform(10, 90, D)], 1)
+    total = int(R.plan(cnt, pos, gt2d, 25.0, D, 1 << 40)[1][-1])
+    slot_box, seg_off, off, n, st = _plan_equals(cnt, pos, gt2d, 25.0, D, total - 1)
+    assert 0 < n < D and st == R.ST_FEW | R.ST_TRUNC and seg_off[-1] == total - 1 and (np.diff(slot_box[:n]) > 0).all()
+
+
 def _plan_limits():
     from frustum_convnet_amd import _native
     a, b = ctypes.c_int(0), ctypes.c_int(0)

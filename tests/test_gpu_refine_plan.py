@@ -131,6 +131,21 @@ def test_plan_equals_the_restatement(B):
     assert n == 0 and st == R.ST_FEW and not seg_off.any() and off.tolist() == [1000] * B + [0] and (slot_unit == 12).all()
 
 
+@pytest.mark.parametrize("S", [1, 3])
+@pytest.mark.parametrize("U", [255, 256, 257])
+def test_plan_where_a_threads_run_goes_from_one_unit_to_two(U, S):
+    """The run-per-thread split is csrc/slot_plan.h's, shared by every plan: over 256 threads, 255 and 256 units are runs of one
+    (the last thread's empty, then not), 257 units are runs of two with threads 129.. owning nothing.  B = U, some units rejected,
+    a capacity one row short of the total."""
+    rs = np.random.RandomState(4 * U + S)
+    cnt = rs.randint(0, 900, (U, S))
+    pos = np.minimum(cnt, rs.randint(0, 40, (U, S))) * (rs.uniform(size=(U, 1)) < 0.7)
+    psz = np.stack([rs.uniform(3, 5, U), rs.uniform(0.5, 2.5, U), rs.uniform(1, 2, U)], 1)
+    total = int(R.plan(cnt, pos, psz, STRIDES, BIG, U, 1 << 40)[2][-1])
+    slot_unit, n, seg_off, off, counts, st = _plan_equals(cnt, pos, psz, U, total - 1)
+    assert 0 < n < U and st == R.ST_FEW | R.ST_TRUNC and seg_off[-1] == total - 1 and counts.sum() == total - 1
+
+
 def test_plan_at_its_smallest_and_at_its_limits():
     one = (np.asarray([[7]]), np.asarray([[2]]), np.asarray([[4.0, 1.6, 1.5]]))
     assert _plan_equals(*one, 1, 100)[3].tolist() == [0, 7]                 # U = S = B = 1

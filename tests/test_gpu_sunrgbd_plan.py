@@ -362,6 +362,23 @@ def test_plan_subsample_and_slots_at_their_smallest_and_over_many_boxes():
     assert r["status"] == R.ST_FEW | R.ST_TRUNC
 
 
+@pytest.mark.parametrize("S", [1, 3])
+@pytest.mark.parametrize("D", [255, 256, 257])
+def test_plan_and_slots_where_a_threads_run_goes_from_one_box_to_two(D, S):
+    """The run-per-thread split is csrc/slot_plan.h's, shared by every plan: over 256 threads, 255 and 256 boxes are runs of one
+    (the last thread's empty, then not), 257 boxes are runs of two with threads 129.. owning nothing.  B = D, some boxes under
+    the bar of positives, a capacity one row short of the total."""
+    rs = np.random.RandomState(4 * D + S)
+    cap = 8
+    cnt = rs.randint(0, 3 * cap, (D, S))
+    labels = [(rs.uniform(size=k) < 0.5).astype(np.int64) for k in cnt.sum(1)]
+    ends = np.cumsum(cnt, 1)
+    pos = np.asarray([[int(l[b - c:b].sum()) for c, b in zip(cs, es)] for l, cs, es in zip(labels, cnt, ends)], dtype=np.int64)
+    total = int(R.plan(cnt, pos, MIN, cap, 1 << 40)[0][-1])
+    r = _chain(cnt, pos, labels, D, total - 1, cap=cap)
+    assert 0 < r["n"] < D and r["status"] == R.ST_FEW | R.ST_TRUNC and r["seg_off"][-1] == total - 1
+
+
 def test_subsample_of_more_rows_than_the_draws_sort_whole():
     """cap = 2048 and boxes on either side of DeviceDraws.limits()[1]: the whole-row sort and the radix select."""
     from frustum_convnet_amd.inputs import DeviceDraws
