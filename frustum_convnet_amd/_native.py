@@ -101,7 +101,8 @@ EXPORTS = ("fcn_arch", "fcn_build_hash", "fcn_stat_replicas", "fcn_query_depth_p
            "fcn_refine_train_plan_limits",
            "fcn_cascade_candidates", "fcn_refine_detect_count", "fcn_refine_detect_fill", "fcn_refine_detect_plan",
            "fcn_frustum_detect_count", "fcn_frustum_detect_fill", "fcn_frustum_detect_plan", "fcn_frustum_detect_plan_limits",
-           "fcn_frustum_fov_plan")
+           "fcn_frustum_fov_plan",
+           "fcn_frustum_sunrgbd_detect_count", "fcn_frustum_sunrgbd_detect_fill", "fcn_frustum_sunrgbd_detect_plan", "fcn_det_rows")
 
 _lib = None
 
@@ -360,6 +361,16 @@ def lib():
         L.fcn_frustum_detect_plan_limits.argtypes = [ctypes.POINTER(ctypes.c_int)] * 2
         L.fcn_frustum_fov_plan.restype = ctypes.c_int
         L.fcn_frustum_fov_plan.argtypes = [c_fp, ctypes.c_int, ctypes.c_int, ctypes.c_int64, c_fp, c_fp, c_fp]
+    if hasattr(L, "fcn_frustum_sunrgbd_detect_plan") or "FCN_LIB_NAME" not in os.environ:
+        L.fcn_frustum_sunrgbd_detect_count.restype = ctypes.c_int
+        L.fcn_frustum_sunrgbd_detect_count.argtypes = sr_in + [c_fp] * 4
+        L.fcn_frustum_sunrgbd_detect_fill.restype = ctypes.c_int
+        L.fcn_frustum_sunrgbd_detect_fill.argtypes = sr_in + [c_fp] * 4
+        L.fcn_frustum_sunrgbd_detect_plan.restype = ctypes.c_int
+        L.fcn_frustum_sunrgbd_detect_plan.argtypes = ([c_fp] * 4 + [ctypes.c_int] * 5 + [ctypes.c_int64] + [ctypes.c_int] * 2 +
+                                                      [c_fp] * 12)
+        L.fcn_det_rows.restype = ctypes.c_int
+        L.fcn_det_rows.argtypes = [c_fp] * 2 + [ctypes.c_int] * 2 + [c_fp, ctypes.c_int] + [c_fp] * 6
     L.fcn_rotate_nms_3d.restype = ctypes.c_int
     L.fcn_rotate_nms_3d.argtypes = [c_fp] * 3 + [ctypes.c_int] * 3 + [ctypes.c_float, ctypes.c_int] + [c_fp] * 3
     _lib = L

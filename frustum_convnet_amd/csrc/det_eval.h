@@ -3,6 +3,8 @@
 //   det_match_kernel       the matching loop of train/sunrgbd_eval/eval_det.py:134-159 (eval_det_cls): every detection against
 //                          every label box of its image and class, greedy in descending score
 //   det_ap_kernel          the curve and the area of :161-169 + voc_ap (:41-72, use_07_metric=False)
+//   det_rows_kernel        the keep lists of the NMS packed group after group (what SunrgbdDetector.detect_frames does on the host
+//                          behind a read-back of keep / cnt), for the capturable chain of evaluate.SunrgbdFrameChain
 // The reference does all of it in Python, one boost / scipy polygon clip per (detection, label) pair on the host; here the
 // corners, the overlaps and the flags stay in HBM and the host reads the AP table.  The clip core is box_iou.h.
 //
@@ -15,8 +17,11 @@
 // which needs no sort and no sequential walk: one pairwise pass inside the group.  Equal scores: the lower input index comes
 // first (np.argsort in the reference is unstable there; this is the documented rule).
 #pragma once
+#include "slot_plan.h"
 
 #define DEV_T 256
+#define DR_MAX_G (FP_T * 256)          // groups of one fcn_det_rows: 256 per thread
+#define DR_ST_OVER 2048                // bit 11: a group's cnt is -1 (the NMS met more than 4096 candidates: no keep list)
 
 // The (BEV IoU, 3-D IoU) of rbbox_iou_3d_pair (box_ops.h:173-260) from two (8,3) corner arrays in the order of compute_box_3d:
 // BEV polygon = corners 6,7,4,5 (x,z), y extents from corners 0 and 4.  What eval_det.py:84-86 get_iou_cc asks per pair.
@@ -249,4 +254,68 @@ extern "C" int fcn_det_ap(const int32_t *tp, const float *scores, const int32_t 
     hipLaunchKernelGGL(det_ap_kernel, dim3(C), dim3(DEV_T), 0, (hipStream_t)stream, a);
     FCN_CHECK_LAUNCH();
     return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// The tail of a capturable detection chain, one workgroup behind fcn_rotate_nms_3d: keep (G, top_k) / cnt (G) -> the kept rows group
+// after group in keep order, their scores, and the groups' offsets -- what SunrgbdDetector.detect_frames builds on the host from a
+// read-back of keep / cnt.  The steps of slot_plan.h: every thread owns a run of groups (sl_run), one fp_block_exscan over the runs'
+// clamped counts gives its base, the offsets go to det_off; behind a barrier the whole workgroup walks the G * top_k keep entries
+// (coalesced) and stores entry (g, j), j < c_g, at det_off[g] + j.  Order-preserving, no atomics on the data.
+struct DetRowsArgs {
+    const int32_t *keep, *cnt;         // (G, top_k), (G)
+    const float *dets;                 // (num_dets, 8)
+    int G, top_k, num_dets;
+    int32_t *det_off;                  // (G+1)
+    int32_t *rows;                     // (G*top_k)
+    float *scores;                     // (G*top_k)
+    int32_t *n_rows, *status;          // (1) each
+};
+
+__global__ __launch_bounds__(FP_T) void det_rows_kernel(DetRowsArgs a)
+{
+    __shared__ int64_t swave[FP_WAVES];
+    const int tid = threadIdx.x, G = a.G, K = a.top_k;
+    int g0, g1;
+    sl_run(G, tid, g0, g1);
+    int64_t mine = 0;
+    bool over = false;
+    for (int g = g0; g < g1; ++g) {
+        const int c = a.cnt[g];
+        over = over || c == -1;
+        mine += c < 0 ? 0 : (c > K ? K : c);
+    }
+    int64_t total;
+    int64_t at = fp_block_exscan(mine, swave, tid, total);
+    for (int g = g0; g < g1; ++g) {
+        const int c = a.cnt[g];
+        a.det_off[g] = (int32_t)at;
+        at += c < 0 ? 0 : (c > K ? K : c);
+    }
+    if (tid == 0) { a.det_off[G] = (int32_t)total; a.n_rows[0] = (int32_t)total; }
+    if (over) atomicOr(a.status, DR_ST_OVER);
+    __syncthreads();                                                       // (det_off: this workgroup's own stores)
+    const int64_t E = (int64_t)G * K;
+    for (int64_t e = tid; e < E; e += FP_T) {
+        const int g = (int)(e / K), j = (int)(e % K);
+        const int c = a.cnt[g];
+        if (j >= (c < 0 ? 0 : (c > K ? K : c))) continue;
+        const int r = a.keep[e];
+        const int64_t o = (int64_t)a.det_off[g] + j;
+        a.rows[o] = r;
+        a.scores[o] = (r >= 0 && r < a.num_dets) ? a.dets[(int64_t)r * 8 + 7] : __builtin_nanf("");   // never dereferenced
+    }
+    for (int64_t e = total + tid; e < E; e += FP_T) { a.rows[e] = -1; a.scores[e] = __builtin_nanf(""); }
+}
+
+extern "C" int fcn_det_rows(const int32_t *keep, const int32_t *cnt, int G, int top_k, const float *dets, int num_dets,
+                            int32_t *det_off, int32_t *rows, float *scores, int32_t *n_rows, int32_t *status, void *stream)
+{
+    if (!keep || !cnt || !det_off || !rows || !scores || !n_rows || !status) return FCN_E_BADARG;
+    if (G < 1 || top_k < 1 || num_dets < 0 || (num_dets > 0 && !dets)) return FCN_E_BADARG;
+    if (G > DR_MAX_G || top_k > 4096 || (int64_t)G * top_k > 0x7fffffff) return FCN_E_LIMIT;
+    DetRowsArgs a;
+    a.keep = keep; a.cnt = cnt; a.dets = dets; a.G = G; a.top_k = top_k; a.num_dets = num_dets; a.det_off = det_off; a.rows = rows;
+    a.scores = scores; a.n_rows = n_rows; a.status = status;
+    return sl_launch(det_rows_kernel, a, stream);
 }

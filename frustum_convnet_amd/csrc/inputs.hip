@@ -505,3 +505,10 @@ extern "C" int fcn_prepare_inputs_refine(const fcn_inp_refine_desc *d, const flo
 // box count, without its read-backs, and the one-workgroup plans between count and fill (fcn_frustum_detect_count / _plan / _fill,
 // fcn_frustum_fov_plan): csrc/frustum_detect_plan.h
 #include "frustum_detect_plan.h"
+
+// ------------------------------------------------------------------------------------------------
+// SUN-RGBD inference without a host read: depth frames + a resident table of 2-D detections -> the five-scale batch's raw points at
+// a fixed number of slots -- the selection of frustum_sunrgbd.h behind a device-resident box count, without its read-backs, and the
+// one-workgroup plan between count and fill with the per-slot subsample slices (fcn_frustum_sunrgbd_detect_count / _plan / _fill):
+// csrc/frustum_sunrgbd_detect_plan.h
+#include "frustum_sunrgbd_detect_plan.h"

@@ -7,6 +7,9 @@ train/sunrgbd_eval/eval_det.py:89-169 (eval_det_cls + voc_ap) clips every detect
 class in Python, matches greedily in descending score and sums the precision / recall curve to an AP per class.  Here no point,
 logit, box or IoU crosses to the host: the keep lists are read between the NMS and the corners (they size the buffers), and the
 result is a dict of device tensors -- the AP table is what a caller reads.  No CPU fallback: CPU tensors raise.
+SunrgbdFrameChain (SunrgbdDetector.frame_link) is detect_frames as ONE capturable sequence of launches at fixed sizes: a
+frustum.SunrgbdDetectSource, the model's detect(rule="sunrgbd") over all F * C (frame, class) groups, the keep lists packed on the
+device (C-ABI fcn_det_rows) and the corners -- nothing is read until result().
 
 KITTI detections and labels to AP per class, difficulty and metric (C-ABI fcn_kitti_*; csrc/kitti_eval.h): kitti_label_rows,
 kitti_eval, kitti_results below -- the reference's train/test_net_det.py:88-123 + train/kitti_eval/evaluate_object_3d_offline.cpp.
@@ -337,3 +340,101 @@ class SunrgbdDetector:
         out["classes"] = classes
         out["det_index"] = dsel
         return out
+
+    def frame_link(self, frame_points, frame_off, K, Rtilt, B, D, capacity, seed, method, thresh, top_k=300, **kw):
+        """detect_frames() as one capturable sequence of launches at fixed sizes: a SunrgbdFrameChain over this detector's model and
+        a frustum.SunrgbdDetectSource on its builder -- frame_points (held), frame_off, K, Rtilt, B (slots), D (rows of the
+        detection table), capacity (rows of the point buffer), seed and, by keyword, cap, point_threshold, sub, choice as the source
+        takes them.  The boxes, their frames, types and scores go into the returned chain's detection table
+        (.source.set_boxes(...), or in place).  frame_link(...).step() then stands where detect_frames(...) stood."""
+        from . import frustum
+        source = frustum.SunrgbdDetectSource(frame_points, frame_off, K, Rtilt, self.input_builder, B, D, capacity, seed, **kw)
+        return SunrgbdFrameChain(self.model, source, method, thresh, top_k)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# SUN-RGBD inference as ONE capturable sequence of launches: depth frames and 2-D boxes to corners, scores and group offsets
+class SunrgbdFrameChain:
+    """Resident depth frames and a resident table of 2-D detections -> the corners and scores of the kept detections, grouped by
+    (frame, class), with no host read, no upload and no validation per step: what SunrgbdDetector.detect_frames does behind its
+    synchronisations, as ONE sequence of launches that can be captured into a hipGraph and replayed on boxes and points overwritten
+    in place (INTEGRATION.md "Capturable SUN-RGBD inference" states the contract).  model: the five-scale PointNetDet in eval mode;
+    source: a frustum.SunrgbdDetectSource on the model's builder; method, thresh, top_k: as PointNetDet.detect.  The NMS groups are
+    ALL F * C (frame, class) pairs, group g = frame * C + class; an empty slot belongs to the spare group F * C, which no NMS
+    workgroup takes.  AP is a sum over the dataset and stays outside: SunrgbdDetector.evaluate takes result() unchanged."""
+
+    KEYS = ("point_cloud", "rot_angle", "rgb_prob", "one_hot", "center_ref1", "center_ref2", "center_ref3", "center_ref4", "center_ref5")
+
+    def __init__(self, model, source, method, thresh, top_k=300):
+        who = "SunrgbdFrameChain"
+        if model.training:
+            raise ValueError("%s: the model must be in eval mode" % who)
+        if method not in ("nms", "top"):
+            raise ValueError("%s: method must be 'nms' or 'top', got %r" % (who, method))
+        top_k = int(top_k)
+        if not (1 <= top_k <= 4096):
+            raise ValueError("%s: top_k must lie in [1, 4096] (the NMS sorts at most 4096 rows of a group), got %d" % (who, top_k))
+        if not np.isfinite(float(thresh)):
+            raise ValueError("%s: thresh must be finite, got %r" % (who, thresh))
+        G = source.F * source.C
+        if not (1 <= G <= 65536) or G * top_k >= 2 ** 31:
+            raise ValueError("%s: F * C = %d groups (at most 65536) of %d rows" % (who, G, top_k))
+        self.model, self.source, self.method, self.thresh, self.top_k, self.G = model, source, method, float(thresh), top_k, G
+        dev = self.device = source.device
+        self.R = source.B * source.builder.L[1]
+        f32, i32 = dict(dtype=torch.float32, device=dev), dict(dtype=torch.int32, device=dev)
+        n = G * top_k
+        # det_off (G+1), n_rows, n_kept, rows (n) and slot_box (B) share ONE int32 buffer: result() reads it in one copy
+        self.ints = torch.zeros((G + 3 + n + source.B,), **i32)
+        self.det_off, self.n_rows, self.n_kept = self.ints[:G + 1], self.ints[G + 1:G + 2], self.ints[G + 2:G + 3]
+        self.rows, self.slot_box = self.ints[G + 3:G + 3 + n], self.ints[G + 3 + n:]
+        self.status = torch.zeros((1,), **i32)
+        self.res = {"dets": torch.zeros((self.R, 8), **f32), "valid": torch.zeros((self.R,), **i32),
+                    "keep": torch.full((G, top_k), -1, **i32), "cnt": torch.zeros((G,), **i32), "rows": self.rows,
+                    "n_rows": self.n_rows, "det_off": self.det_off, "corners": torch.zeros((n, 8, 3), **f32),
+                    "scores": torch.zeros((n,), **f32)}
+
+    def step(self):
+        """Enqueues on the current stream source.step(), model.detect(rule="sunrgbd") with the slots' groups, fcn_det_rows and
+        fcn_box3d_corners -- and nothing else: no host read, no upload (capturable).  Returns a dict, the same device tensors every
+        step: dets (B * L2, 8), valid, keep (G, top_k), cnt (G) as PointNetDet.detect returns them; rows (G * top_k) int32 the kept
+        rows group after group in keep order (-1 behind n_rows), n_rows (1), det_off (G+1) int32, corners (G * top_k, 8, 3) and scores
+        (G * top_k) of those rows (NaN behind n_rows); for inspection batch (the model's input), slot_box (B) and n_kept (1)."""
+        src, res, G = self.source, self.res, self.G
+        got = src.step()
+        batch = {k: got[k] for k in self.KEYS if k in got}
+        d, v, k, c = self.model.detect(batch, unit_group=src.slot_group, num_groups=G, method=self.method, thresh=self.thresh,
+                                       top_k=self.top_k, rule="sunrgbd")
+        if tuple(d.shape) != (self.R, 8) or tuple(k.shape) != (G, self.top_k):      # (attributes: nothing is read)
+            raise ValueError("SunrgbdFrameChain.step: the model must give %d rows and %d groups of %d" % (self.R, G, self.top_k))
+        res["dets"].copy_(d); res["valid"].copy_(v); res["keep"].copy_(k); res["cnt"].copy_(c)
+        self.slot_box.copy_(src.slot_box); self.n_kept.copy_(src.n_kept)
+        L, p = _native.lib(), (lambda x: x.data_ptr())
+        with torch.cuda.device(self.device):
+            s = _native.current_stream(self.device)
+            _native.check(L.fcn_det_rows(p(res["keep"]), p(res["cnt"]), G, self.top_k, p(res["dets"]), self.R, p(self.det_off),
+                                         p(self.rows), p(res["scores"]), p(self.n_rows), p(self.status), s), "fcn_det_rows")
+            _native.check(L.fcn_box3d_corners(p(res["dets"]), self.R, p(self.rows), G * self.top_k, p(res["corners"]), s),
+                          "fcn_box3d_corners")
+        out = dict(res)
+        out.update(batch=batch, slot_box=self.slot_box, n_kept=self.n_kept)
+        return out
+
+    def result(self):
+        """The dict SunrgbdDetector.detect_frames returns, from the last step() -- ONE synchronisation: n_rows, det_off (and rows,
+        the slots' boxes) are read in one copy.  The groups are all F * C (frame, class) pairs in that order; rows, corners and
+        scores are cut to the n_rows kept rows (views of the chain's tensors: the next step() overwrites them)."""
+        src, G, res = self.source, self.G, self.res
+        h = self.ints.cpu().numpy().astype(np.int64)
+        n, nk = int(h[G + 1]), int(h[G + 2])
+        g = np.arange(G, dtype=np.int64)
+        return {"dets": res["dets"], "valid": res["valid"], "keep": res["keep"], "cnt": res["cnt"], "rows": h[G + 3:G + 3 + n].copy(),
+                "corners": res["corners"][:n], "scores": res["scores"][:n], "det_off": h[:G + 1].copy(), "group_frame": g // src.C,
+                "group_class": g % src.C, "kept": h[G + 3 + G * self.top_k:][:nk].copy()}
+
+    def check(self):
+        """check() of the source and of the tail in one: reads their status words (a synchronisation), raises ValueError naming the
+        bits set since the last check() and clears them."""
+        from .frustum import check_status, STATUS_BITS
+        src = self.source
+        check_status("SunrgbdFrameChain", (src.status, src.draws.status, src.draws_sub.status, self.status), STATUS_BITS)

@@ -18,7 +18,9 @@ on the device, a one-workgroup plan in place of the host's kept list and prefix 
 training path, with the frustum subsamples drawn on the device as well (csrc/frustum_sunrgbd_plan.h).  FrameDetectSource is the
 KITTI INFERENCE path the same way: resident frames and a resident table of 2-D detections -> the first-stage batch at a fixed number
 of slots and, when asked, the image-FOV search set of the second stage (fcn_frustum_detect_count / _plan / _fill,
-fcn_frustum_fov_plan, csrc/frustum_detect_plan.h).
+fcn_frustum_fov_plan, csrc/frustum_detect_plan.h).  SunrgbdDetectSource is the SUN-RGBD inference path the same way, the frustum
+subsamples drawn on the device and every (frame, class) NMS group numbered by the plan (fcn_frustum_sunrgbd_detect_count / _plan /
+_fill, csrc/frustum_sunrgbd_detect_plan.h); evaluate.SunrgbdFrameChain carries it on to corners and scores.
 No CPU fallback.
 """
 import ctypes
@@ -426,7 +428,8 @@ STATUS_BITS = ((1, "bit 0: a slot had no row to draw from (its choice row is zer
                (4, "bit 2: the selected rows exceed the capacity of the point buffer (the overflow was dropped)"),
                (16, "bit 4: a box had no valid perturbation within the attempt cap (its label box was used as it is)"),
                (256, "bit 8: more boxes survived than the batch has slots (the rest were dropped)"),
-               (1024, "bit 10: n_boxes lies outside [0, D] or a box's frame outside [0, F) (the overflow or the box was ignored)"))
+               (1024, "bit 10: n_boxes lies outside [0, D] or a box's frame outside [0, F) -- SUN-RGBD: or its class outside [0, C) -- (the overflow or the box was ignored)"),
+               (2048, "bit 11: an NMS group held more than 4096 candidates (it has no keep list: none of its rows was kept)"))
 
 
 class FrameTrainSource:
@@ -1006,3 +1009,194 @@ class FrameDetectSource:
         the bits set since the last check() and clears them.  Bit 0 is the draws' own: an EMPTY slot has no row to draw from either,
         so it is set by every step with fewer survivors than slots."""
         check_status("FrameDetectSource", (self.status, self.draws.status), STATUS_BITS)
+
+
+# ------------------------------------------------------------------------------------------------
+# The SUN-RGBD INFERENCE input as ONE capturable sequence of launches (csrc/frustum_sunrgbd_detect_plan.h)
+class SunrgbdDetectSource:
+    """Resident depth frames and a resident table of at most D 2-D detections -> the SunrgbdInputBuilder inference batch at a FIXED
+    batch size B, every step, with no host read and no upload: what sunrgbd_candidates (with its host rng.choice per large frustum) +
+    SunrgbdInputBuilder.build_device do behind their synchronisations, as one sequence of launches that can be captured into a
+    hipGraph and replayed on boxes and points overwritten in place (INTEGRATION.md "Capturable SUN-RGBD inference" states the
+    contract).  It mirrors FrameDetectSource.
+    frame_points: a contiguous (n >= 1, >= 3) float32 device tensor of upright-depth rows, HELD, not copied -- a caller may overwrite
+    it in place between steps; frame_off, K, Rtilt as sunrgbd_candidates takes them (copied to the device; S, the segments of the
+    longest frame, is fixed here: frames written later must not be longer than S * fcn_frustum_select_seg() rows, nor move their
+    offsets); builder: a SunrgbdInputBuilder; B: slots of the batch; D: rows of the detection table (B <= D <= 2048; survivors beyond
+    B, in box order, are dropped and flagged); capacity: rows of the point buffer (rows beyond it are dropped and flagged, and every
+    later count is the STORED count); seed: two DeviceDraws keyed seed (per-sample resample) and seed + 1 (frustum subsamples), each
+    one step further after every step(), whatever the options; cap / point_threshold: sunrgbd_candidates' and build_device's.
+    The detection table has D + 1 rows: boxes2d (D+1,4) fp64 xmin ymin xmax ymax, box_frame, box_class (index into builder.classes)
+    (D+1) int32, box_prob (D+1) fp32 and n_boxes (1) int32, the live rows.  A 2-D detector overwrites rows 0..n_boxes-1 and n_boxes in
+    place between steps; set_boxes() fills them from host sequences.  Row D is the spare row an empty slot gathers -- a unit box,
+    frame 0, class 0, probability 0 -- written here once: leave it alone.  There is no box_group: a box's NMS group is
+    frame * C + class (C = len(builder.classes)), F * C for an empty slot.
+    sub / choice (device tables, to reproduce a recorded run or to feed the existing path the same draws): sub (B * cap) int32 the
+    per-slot subsample table in place of the device's draw -- slot i's `cap` indices into its stored rows at sub_off[i], the packed
+    layout of the plan; choice (B, N) int32 indices into each slot's RECORD (its subsample where it has one) in place of the
+    resample draw.  With either, step() clamps the composed indices to the slot's stored rows on the device (a few extra elementwise
+    launches): an index never points at a row that was not stored.
+    Everything is validated here, once, on the host; step() validates nothing and reads nothing."""
+
+    def __init__(self, frame_points, frame_off, K, Rtilt, builder, B, D, capacity, seed, cap=SUNRGBD_CAP, point_threshold=SUNRGBD_MIN,
+                 sub=None, choice=None):
+        from .inputs import DeviceDraws
+        who = "SunrgbdDetectSource"
+        if not (isinstance(frame_points, torch.Tensor) and frame_points.is_cuda and frame_points.dtype == torch.float32 and
+                frame_points.is_contiguous() and frame_points.dim() == 2 and frame_points.shape[0] >= 1 and not frame_points.requires_grad):
+            raise ValueError("%s: frame_points must be a contiguous (n >= 1, >= 3) float32 device tensor (it is held, not copied)" % who)
+        pts, foff, F, ps, S = _frames(who, frame_points, frame_off, resident=True)
+        dev = frame_points.device
+        cal = []
+        for name, m in (("K", K), ("Rtilt", Rtilt)):
+            t = torch.as_tensor(m).to(device=dev, dtype=torch.float64).contiguous()
+            if t.numel() != F * 9:
+                raise ValueError("%s: %s must hold %d x 9 numbers, got %s" % (who, name, F, tuple(t.shape)))
+            cal.append(t.view(F, 9))
+        if builder.device.type != "cuda":
+            raise RuntimeError("frustum_convnet_amd: input construction is a HIP kernel (MI355X only); no CPU fallback")
+        B, D, capacity, cap, point_threshold = int(B), int(D), int(capacity), int(cap), int(point_threshold)
+        max_d, max_segs, max_cap = self.limits()
+        N, C = builder.npoints, len(builder.classes)
+        if not (1 <= B <= D <= max_d):
+            raise ValueError("%s: need 1 <= B <= D <= %d, got B = %d, D = %d" % (who, max_d, B, D))
+        if D * S > max_segs:
+            raise ValueError("%s: D * S = %d * %d segments exceed the plan's %d" % (who, D, S, max_segs))
+        if not (1 <= cap <= max_cap) or not (1 <= N <= max_cap):
+            raise ValueError("%s: cap and the builder's npoints must lie in [1, %d], got %d, %d" % (who, max_cap, cap, N))
+        if capacity < 1:
+            raise ValueError("%s: capacity must be >= 1 row, got %d" % (who, capacity))
+        if F * C >= 2 ** 31 or abs(point_threshold) >= 2 ** 31:
+            raise ValueError("%s: F * C = %d groups and point_threshold = %d must fit int32" % (who, F * C, point_threshold))
+        for name, t, n in (("sub", sub, B * cap), ("choice", choice, B * N)):
+            if t is not None and not (isinstance(t, torch.Tensor) and t.device == dev and t.dtype == torch.int32 and t.is_contiguous()
+                                      and t.numel() == n):
+                raise ValueError("%s: %s must be a contiguous int32 tensor of %d entries on %s" % (who, name, n, dev))
+        self.device, self.builder = dev, builder
+        self.B, self.D, self.F, self.C, self.S, self.ps, self.capacity = B, D, F, C, S, ps, capacity
+        self.cap, self.point_threshold = cap, point_threshold
+        f32, f64, i32, i64 = (dict(dtype=t, device=dev) for t in (torch.float32, torch.float64, torch.int32, torch.int64))
+        # ---- resident: the frames (held), the calibration, the detection table with its spare row D
+        self.frames = (pts, foff, cal[0], cal[1])
+        self.boxes2d = torch.zeros((D + 1, 4), **f64)
+        self.boxes2d[D] = torch.tensor([0.0, 0.0, 1.0, 1.0], **f64)
+        self.box_frame, self.box_class = torch.zeros((D + 1,), **i32), torch.zeros((D + 1,), **i32)
+        self.box_prob, self.n_boxes = torch.zeros((D + 1,), **f32), torch.zeros((1,), **i32)
+        self.eye = torch.eye(C, **f32)
+        self.draws, self.draws_sub = DeviceDraws(int(seed), builder.device), DeviceDraws(int(seed) + 1, builder.device)
+        self.status = torch.zeros((1,), **i32)
+        # ---- every intermediate.  angle has D + 1 entries as well: entry D is what an empty slot gathers, zero, never written by a kernel
+        self.angle, self.seg_cnt = torch.zeros((D + 1,), **f64), torch.zeros((D, S), **i32)
+        self.slot_box, self.n_kept = torch.full((B,), D, **i32), torch.zeros((1,), **i32)
+        self.slot_frame, self.slot_class = torch.zeros((B,), **i32), torch.zeros((B,), **i32)
+        self.slot_group = torch.full((B,), F * C, **i32)
+        self.seg_off, self.off, self.counts = torch.zeros((D * S + 1,), **i64), torch.zeros((B + 1,), **i64), torch.zeros((B,), **i64)
+        self.cnt32, self.sub_off = torch.zeros((B,), **i32), torch.zeros((B + 1,), **i64)
+        self.sub_start, self.sub_len = torch.zeros((B,), **i64), torch.zeros((B,), **i32)
+        self.fixed_sub, self.fixed_choice = sub is not None, choice
+        self.sub = sub.view(-1) if self.fixed_sub else torch.zeros((B * cap,), **i32)
+        # the spare row is what an empty slot's all-zero choice row reads: fcn_prepare_inputs_sunrgbd_infer indexes off[b] + choice
+        self.points = torch.zeros((capacity + 1, ps), **f32)
+        self.t = {"raw": self.points, "off": self.off, "choice": torch.zeros((B, N), **i32), "fangle": torch.zeros((B,), **f64),
+                  "box2d": torch.zeros((B, 4), **f64), "K": torch.zeros((B, 9), **f64), "R": torch.zeros((B, 9), **f64), "B": B,
+                  "pt_stride": ps}
+        self.scalars = tuple(torch.zeros((B,), **f64) for _ in range(3))            # the draw's coin, normal and hshift: unused
+        self.out = builder.alloc_infer(B)
+
+    @staticmethod
+    def limits():
+        """(the largest D, the largest D * S, the largest cap and npoints) of the kernels."""
+        a, b, c, d = (ctypes.c_int(0) for _ in range(4))
+        L = _native.lib()
+        _native.check(L.fcn_frustum_detect_plan_limits(ctypes.byref(a), ctypes.byref(b)), "fcn_frustum_detect_plan_limits")
+        _native.check(L.fcn_draw_limits(ctypes.byref(c), ctypes.byref(d)), "fcn_draw_limits")
+        return a.value, b.value, c.value
+
+    def set_boxes(self, boxes2d, box_frame, types, prob):
+        """Fills rows 0..n-1 of the detection table and n_boxes in place from host sequences of n <= D boxes (validated here: finite
+        boxes, frames in [0, F), class names of builder.classes, finite scores).  An upload: not for a captured region."""
+        who = "SunrgbdDetectSource.set_boxes"
+        host = lambda a: (a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a))
+        boxes = np.ascontiguousarray(host(boxes2d), dtype=np.float64).reshape(-1, 4)
+        fr, pr = np.ascontiguousarray(host(box_frame)).reshape(-1), np.ascontiguousarray(host(prob), dtype=np.float32).reshape(-1)
+        n = len(boxes)
+        types = [str(t) for t in types]
+        if n > self.D or len(fr) != n or len(pr) != n or len(types) != n:
+            raise ValueError("%s: %d boxes (at most %d), %d frames, %d types, %d scores" % (who, n, self.D, len(fr), len(types), len(pr)))
+        if n and (fr.dtype.kind not in "iu" or fr.min() < 0 or fr.max() >= self.F):
+            raise ValueError("%s: frames must be integers in [0, %d)" % (who, self.F))
+        if not (np.isfinite(boxes).all() and np.isfinite(pr).all()):
+            raise ValueError("%s: boxes and scores must be finite" % who)
+        cls = [self.builder.classes.index(t) if t in self.builder.classes else -1 for t in types]
+        if n and min(cls) < 0:
+            raise ValueError("%s: type %r is not one of %r" % (who, types[cls.index(-1)], tuple(self.builder.classes)))
+        up = lambda a, dt: torch.from_numpy(np.ascontiguousarray(np.asarray(a, dtype=dt)))
+        if n:
+            self.boxes2d[:n].copy_(up(boxes, np.float64))
+            self.box_prob[:n].copy_(up(pr, np.float32))
+            for dst, src in ((self.box_frame, fr), (self.box_class, cls)):
+                dst[:n].copy_(up(src, np.int32))
+        self.n_boxes.fill_(n)
+        return self
+
+    def step(self):
+        """Enqueues one batch on the current stream -- count, plan, fill, fcn_frustum_subsample_draw, the gathers through slot_box,
+        fcn_draw_batch_sliced, fcn_prepare_inputs_sunrgbd_infer -- and nothing else: no allocation, no host read, no upload
+        (capturable).  Returns the batch dict of SunrgbdInputBuilder.build_device() without 'kept', at batch size B -- an empty slot
+        holds the spare row's frustum over no rows -- plus slot_box (B) int32 the box of each slot (D: empty), slot_frame, slot_class,
+        slot_group (B) int32 its frame, class and group frame * C + class (F * C: empty) and n_kept (1) the filled slots; the same
+        tensors every step.  self.sub / self.sub_off hold the step's subsample table; check() reads the status words."""
+        L, dev, bld = _native.lib(), self.device, self.builder
+        B, D, S, F, t, out = self.B, self.D, self.S, self.F, self.t, self.out
+        p = lambda x: x.data_ptr()
+        pts, foff, K, R = self.frames
+        with torch.cuda.device(dev):
+            s = _native.current_stream(dev)
+            args = (p(pts), p(foff), F, self.ps, p(K), p(R), p(self.boxes2d), p(self.box_frame), D, S, p(self.n_boxes))
+            _native.check(L.fcn_frustum_sunrgbd_detect_count(*args, p(self.angle), p(self.seg_cnt), s), "fcn_frustum_sunrgbd_detect_count")
+            _native.check(L.fcn_frustum_sunrgbd_detect_plan(p(self.seg_cnt), p(self.box_frame), p(self.box_class), p(self.n_boxes),
+                                                            self.point_threshold, self.cap, D, S, B, self.capacity, F, self.C,
+                                                            p(self.slot_box), p(self.n_kept), p(self.seg_off), p(self.off), p(self.counts),
+                                                            p(self.cnt32), p(self.sub_off), p(self.sub_start), p(self.sub_len),
+                                                            p(self.slot_group), p(self.status), s), "fcn_frustum_sunrgbd_detect_plan")
+            _native.check(L.fcn_frustum_sunrgbd_detect_fill(*args, p(self.seg_off), p(self.points), s), "fcn_frustum_sunrgbd_detect_fill")
+            _native.check(L.fcn_frustum_subsample_draw(p(self.cnt32), p(self.sub_off), 0 if self.fixed_sub else B, self.cap,
+                                                       self.draws_sub.seed, p(self.draws_sub.state), 1, p(self.sub),
+                                                       p(self.draws_sub.status), s), "fcn_frustum_subsample_draw")
+            for src, dst in ((self.angle, t["fangle"]), (self.boxes2d, t["box2d"]), (self.box_prob.view(D + 1, 1), out["rgb_prob"]),
+                             (self.box_frame, self.slot_frame), (self.box_class, self.slot_class)):
+                torch.index_select(src, 0, self.slot_box, out=dst)
+            torch.index_select(K, 0, self.slot_frame, out=t["K"])
+            torch.index_select(R, 0, self.slot_frame, out=t["R"])
+            if "one_hot" in out:
+                torch.index_select(self.eye, 0, self.slot_class, out=out["one_hot"])
+            dd = self.draws
+            desc = _native.DrawDesc(B, bld.npoints, 0, 0)
+            _native.check(L.fcn_draw_batch_sliced(ctypes.byref(desc), p(self.counts), p(self.sub), p(self.sub_start), p(self.sub_len),
+                                                  dd.seed, p(dd.state), p(t["choice"]), p(self.scalars[0]), p(self.scalars[1]),
+                                                  p(self.scalars[2]), p(dd.status), s), "fcn_draw_batch_sliced")
+            if self.fixed_sub or self.fixed_choice is not None:
+                self._compose()
+            bld.launch_infer(t, out)
+        res = dict(out)
+        res.update(slot_box=self.slot_box, slot_frame=self.slot_frame, slot_class=self.slot_class, slot_group=self.slot_group,
+                   n_kept=self.n_kept)
+        return res
+
+    def _compose(self):
+        """The override tables into t["choice"]: a given choice indexes the slot's record, so it goes through the slot's subsample
+        slice where it has one; whatever comes out is clamped to the slot's stored rows (elementwise launches, no host read)."""
+        t, last = self.t, (self.counts - 1).clamp_(min=0).view(-1, 1)
+        if self.fixed_choice is not None:
+            ch = self.fixed_choice.view(self.B, -1).to(torch.int64)
+            idx = (ch + self.sub_start.view(-1, 1)).clamp_(0, self.sub.numel() - 1)
+            ch = torch.where(self.sub_len.view(-1, 1) > 0, self.sub.to(torch.int64)[idx], ch)
+        else:
+            ch = t["choice"].to(torch.int64)
+        t["choice"].copy_(torch.minimum(ch.clamp_(min=0), last))
+
+    def check(self):
+        """Reads the status words of the plan and the two generators (a synchronisation: not for a captured region); raises
+        ValueError naming the bits set since the last check() and clears them.  Bit 0 is the draws' own: an EMPTY slot has no row to
+        draw from either, so it is set by every step with fewer survivors than slots."""
+        check_status("SunrgbdDetectSource", (self.status, self.draws.status, self.draws_sub.status), STATUS_BITS)

@@ -529,18 +529,7 @@ class SunrgbdInputBuilder:
         t = {"raw": sel["points"], "choice": self._choice(draws, [sel["sub"][d] for d in kept]),
              "off": pick(sel["off"]),                                         # the kernel reads a sample's first row only
              "fangle": pick(sel["frustum_angle"]), "box2d": pick(sel["box2d"]), "K": Kd, "R": Rd}
-        f32 = dict(dtype=torch.float32, device=dev)
-        out = {"point_cloud": torch.empty((B, 3, N), **f32), "rot_angle": torch.empty((B, 1), **f32)}
-        for s in range(5):
-            out["center_ref%d" % (s + 1)] = torch.empty((B, 3, self.L[s]), **f32)
-        desc = Inp5Desc(B, N, int(sel["points"].shape[1]), (ctypes.c_int32 * 5)(*self.L), (ctypes.c_double * 5)(*self.strides),
-                        self.max_depth, 0, 0)
-        refs = (ctypes.c_void_p * 5)(*[out["center_ref%d" % (s + 1)].data_ptr() for s in range(5)])
-        p = lambda x: x.data_ptr()
-        with torch.cuda.device(dev):
-            _native.check(_native.lib().fcn_prepare_inputs_sunrgbd_infer(
-                ctypes.byref(desc), p(t["raw"]), p(t["off"]), p(t["choice"]), p(t["fangle"]), p(t["box2d"]), p(t["K"]), p(t["R"]),
-                p(out["point_cloud"]), refs, p(out["rot_angle"]), _native.current_stream(dev)), "fcn_prepare_inputs_sunrgbd_infer")
+        out = self.launch_infer(dict(t, B=B, pt_stride=int(sel["points"].shape[1])), self.alloc_infer(B))
         for v in t.values():
             v.record_stream(torch.cuda.current_stream(dev))
         out["rgb_prob"] = up(np.asarray(prob, dtype=np.float32)[kept].reshape(B, 1))
@@ -549,6 +538,35 @@ class SunrgbdInputBuilder:
             oh[np.arange(B), [self.classes.index(types[i]) for i in kept]] = 1.0
             out["one_hot"] = up(oh)
         out["kept"] = kept
+        return out
+
+    def alloc_infer(self, B):
+        """Output tensors of launch_infer() for a batch of B frustums: the dict of build_device() without 'kept' -- point_cloud,
+        rot_angle, center_ref1..5, rgb_prob (B,1) and, with one_hot, one_hot (B, classes), both zeros for the caller to fill."""
+        dev, N = self.device, self.npoints
+        f32 = dict(dtype=torch.float32, device=dev)
+        out = {"point_cloud": torch.empty((B, 3, N), **f32), "rot_angle": torch.empty((B, 1), **f32)}
+        for s in range(5):
+            out["center_ref%d" % (s + 1)] = torch.empty((B, 3, self.L[s]), **f32)
+        out["rgb_prob"] = torch.zeros((B, 1), **f32)
+        if self.one_hot:
+            out["one_hot"] = torch.zeros((B, len(self.classes)), **f32)
+        return out
+
+    def launch_infer(self, t, out):
+        """ONE launch of fcn_prepare_inputs_sunrgbd_infer on the current stream: device tensors `t` -- raw, off, choice (indices
+        into the full packed selection), fangle, box2d, K, R, B, pt_stride -- into the caller-owned `out` of alloc_infer(): no
+        allocation, no host work besides the call (capturable into a hipGraph).  rgb_prob / one_hot are the caller's to write.
+        Returns out."""
+        dev = self.device
+        desc = Inp5Desc(t["B"], self.npoints, t["pt_stride"], (ctypes.c_int32 * 5)(*self.L), (ctypes.c_double * 5)(*self.strides),
+                        self.max_depth, 0, 0)
+        refs = (ctypes.c_void_p * 5)(*[out["center_ref%d" % (s + 1)].data_ptr() for s in range(5)])
+        p = lambda x: x.data_ptr()
+        with torch.cuda.device(dev):
+            _native.check(_native.lib().fcn_prepare_inputs_sunrgbd_infer(
+                ctypes.byref(desc), p(t["raw"]), p(t["off"]), p(t["choice"]), p(t["fangle"]), p(t["box2d"]), p(t["K"]), p(t["R"]),
+                p(out["point_cloud"]), refs, p(out["rot_angle"]), _native.current_stream(dev)), "fcn_prepare_inputs_sunrgbd_infer")
         return out
 
     def build_device_train(self, sel, K, Rtilt, types, draws=None, with_seg=True):

@@ -1137,6 +1137,58 @@ int fcn_frustum_detect_plan_limits(int *max_d, int *max_segs);
  * longer than the frame.  NULL pointers, F < 0, S < 1 or capacity < 0: FCN_E_BADARG; F * S > 65536: FCN_E_LIMIT. */
 int fcn_frustum_fov_plan(const int32_t *seg_cnt, int F, int S, int64_t capacity, int64_t *seg_off, int64_t *fov_off, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * SUN-RGBD inference with no host read between its launches (csrc/frustum_sunrgbd_detect_plan.h, csrc/det_eval.h; INTEGRATION.md
+ * "Capturable SUN-RGBD inference" states the contract bit for bit, tests/sunrgbd_detect_plan_ref.py restates it in numpy): count,
+ * plan, fill over a resident table of at most D 2-D detections, and the tail behind the NMS -- none of them reads anything back,
+ * allocates or synchronises, so the sequence can be captured into a hipGraph.  Status bits (*status: one int32 on the device,
+ * OR-ed, never cleared here): bit 2 (4) rows dropped because the total exceeds the capacity; bit 8 (256) more surviving boxes than
+ * B; bit 10 (1024) *n_boxes outside [0, D] (taken as 0 / D) or a box below *n_boxes whose frame is outside [0, F) or whose class is
+ * outside [0, C) (ignored, never dereferenced); bit 11 (2048) fcn_det_rows met a group whose cnt is -1.  (Bit 0 is the draws';
+ * fewer survivors than B is the normal case here and sets nothing.)
+ *
+ * fcn_frustum_sunrgbd_detect_count / _fill: the selection of fcn_frustum_sunrgbd_count / _fill -- the same fp64 predicate, the same
+ * frustum_angle, the same stored rows bit for bit -- without the read-back of box_frame and frame_off, and behind n_boxes (1) int32
+ * on the device: box d is skipped silently when d >= *n_boxes or its frame is outside [0, F) -- its counts are 0, its entry of
+ * frustum_angle is NOT written, nothing of it is dereferenced or stored, the calls return 0.  "No frame is longer than
+ * S * fcn_frustum_select_seg() rows" is the caller's duty: rows beyond S segments would silently not be searched.
+ * Refusals as fcn_frustum_sunrgbd_count / _fill, plus n_boxes == NULL: FCN_E_BADARG. */
+int fcn_frustum_sunrgbd_detect_count(const float *frame_pts, const int64_t *frame_off, int F, int pt_stride, const double *K,
+                                     const double *Rtilt, const double *boxes, const int32_t *box_frame, int D, int S,
+                                     const int32_t *n_boxes, double *frustum_angle, int32_t *seg_cnt, void *stream);
+int fcn_frustum_sunrgbd_detect_fill(const float *frame_pts, const int64_t *frame_off, int F, int pt_stride, const double *K,
+                                    const double *Rtilt, const double *boxes, const int32_t *box_frame, int D, int S,
+                                    const int32_t *n_boxes, const int64_t *seg_off, float *out_pts, void *stream);
+/* fcn_frustum_sunrgbd_detect_plan: what the host does between count and fill and in SunrgbdInputBuilder.build_device, as ONE
+ * launch of one workgroup.  seg_cnt (D,S) int32 from fcn_frustum_sunrgbd_detect_count, box_frame (D), box_class (D), n_boxes (1).
+ * With count_d = the sum of box d's positive segment counts, box d survives iff d < min(*n_boxes, D), its frame lies in [0, F), its
+ * class in [0, C) and min(count_d, cap) >= max(1, point_threshold) -- build_device's rule on subsampled_counts.  The first B
+ * survivors in box order take the slots: slot_box (B) int32, D for an empty slot; *n_kept.  seg_off (D*S+1) int64: the exclusive
+ * prefix sum of the slot-holding boxes' counts, every entry clamped to capacity (boxes without a slot get empty slices: the fill
+ * stores nothing for them).  off (B+1) int64: a filled slot's first row, capacity (the spare row behind the buffer) for an empty
+ * one, off[B] = the rows stored.  counts (B) int64 and cnt32 (B) int32: the STORED rows per slot.  slot_group (B) int32:
+ * frame * C + class of the slot's box, F * C (the spare group) for an empty slot.  The subsample table is laid out PER SLOT,
+ * packed: sub_off (B+1) int64 is the exclusive prefix sum over the slots of (counts[i] > cap ? cap : 0) -- at most B * cap entries
+ * -- so that (cnt32, sub_off, B) is what fcn_frustum_subsample_draw takes as (cnt_stored, sub_off, D); sub_start (B) int64 /
+ * sub_len (B) int32 = sub_off[i] / cap where the slot stored more than cap rows, else 0 / 0: what fcn_draw_batch_sliced takes.
+ * The subsample is decided on the STORED rows.  Table rows at or beyond *n_boxes are never read.  Every output is written on every
+ * call.  NULL pointers, D < 0, S < 1, B < 1, capacity < 0, cap < 1, F < 0, C < 1 or F * C > 2^31 - 1: FCN_E_BADARG; D or B > 2048
+ * or D * S > 65536 (fcn_frustum_detect_plan_limits): FCN_E_LIMIT; nothing written. */
+int fcn_frustum_sunrgbd_detect_plan(const int32_t *seg_cnt, const int32_t *box_frame, const int32_t *box_class,
+                                    const int32_t *n_boxes, int point_threshold, int cap, int D, int S, int B, int64_t capacity, int F,
+                                    int C, int32_t *slot_box, int32_t *n_kept, int64_t *seg_off, int64_t *off, int64_t *counts,
+                                    int32_t *cnt32, int64_t *sub_off, int64_t *sub_start, int32_t *sub_len, int32_t *slot_group,
+                                    int32_t *status, void *stream);
+/* fcn_det_rows: the tail behind fcn_rotate_nms_3d, one launch of one workgroup.  keep (G, top_k) int32, cnt (G) int32, dets
+ * (num_dets, 8) fp32.  With c_g = clamp(cnt[g], 0, top_k): det_off (G+1) int32 the exclusive prefix sum of c_g; rows (G*top_k) int32
+ * keep[g, 0..c_g) group after group, -1 behind det_off[G]; scores (G*top_k) fp32 = dets[row, 7], NaN where the row is -1 or outside
+ * [0, num_dets) -- such a row is never dereferenced; *n_rows = det_off[G].  A group with cnt == -1 (more than 4096 candidates) sets
+ * bit 11 (2048) of *status and contributes no row.  Order-preserving scans, no atomics on the data.  fcn_box3d_corners(dets,
+ * num_dets, rows, G * top_k, ...) follows as it is.  NULL pointers (dets with num_dets > 0), G < 1, top_k < 1 or num_dets < 0:
+ * FCN_E_BADARG; G > 65536, top_k > 4096 or G * top_k > 2^31 - 1: FCN_E_LIMIT; nothing written. */
+int fcn_det_rows(const int32_t *keep, const int32_t *cnt, int G, int top_k, const float *dets, int num_dets, int32_t *det_off,
+                 int32_t *rows, float *scores, int32_t *n_rows, int32_t *status, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
