@@ -16,16 +16,18 @@ Training the refinement stage on the first stage's output (extract_frustum_det_d
 select, count the positives, reject) is match_detections + draw_box3d_jitter + refine_training_candidates (C-ABI fcn_refine_match,
 fcn_refine_label_count / _fill, csrc/refine_label.h) and RefineInputBuilder.build_device_train.  RefineTrainSource is the same link
 as ONE capturable sequence of launches at a fixed batch size and fixed window counts, with no host read (C-ABI
-fcn_refine_train_match / _count / _plan / _fill, fcn_box3d_jitter_draw, csrc/refine_plan.h).
+fcn_refine_train_match / _count / _plan / _fill, fcn_box3d_jitter_draw, csrc/refine_plan.h).  The constructors' shared checks, the
+spare corners and the batch skeleton of RefineTrainSource and CascadeLink are resident.py's, as for the four sources of frustum.py.
 """
 import ctypes
 
 import numpy as np
 import torch
 
-from . import _native
+from . import _native, resident
 from .detect import _need_cuda
-from .frustum import _frames, check_status
+from .frustum import FrameDetectSource, _frames, _packed, check_status
+from .inputs import DeviceDraws
 
 
 def refine_candidates(frame_points, frame_off, dets, cand_row, cand_frame, ratio=1.2):
@@ -39,13 +41,7 @@ def refine_candidates(frame_points, frame_off, dets, cand_row, cand_frame, ratio
     and counts (D) int64 on the host: the one read between the two launches."""
     pts, foff, F, ps, _ = _frames("refine_candidates", frame_points, frame_off)       # (one workgroup per box: no segments)
     dev = frame_points.device
-    d8 = dets.detach().to(device=dev, dtype=torch.float32).contiguous()
-    if d8.dim() != 2 or d8.shape[1] != 8:
-        raise ValueError("refine_candidates: dets must be (R, 8), got %s" % (tuple(dets.shape),))
-    crow = torch.as_tensor(cand_row).to(device=dev, dtype=torch.int32).contiguous().view(-1)
-    cframe = torch.as_tensor(cand_frame).to(device=dev, dtype=torch.int32).contiguous().view(-1)
-    if crow.numel() != cframe.numel():
-        raise ValueError("refine_candidates: %d rows but %d frames" % (crow.numel(), cframe.numel()))
+    d8, crow, cframe = _candidates("refine_candidates", frame_points, dets, cand_row, cand_frame)
     R, D = int(d8.shape[0]), int(crow.numel())
     f64 = dict(dtype=torch.float64, device=dev)
     out = {"pred_box3d": torch.zeros((D, 8, 3), **f64), "pred_angle": torch.zeros((D,), **f64),
@@ -57,16 +53,13 @@ def refine_candidates(frame_points, frame_off, dets, cand_row, cand_frame, ratio
                                                 out["pred_size"].data_ptr(), out["cnt"].data_ptr(),
                                                 _native.current_stream(dev)), "fcn_refine_select_count")
         counts = out["cnt"].cpu().numpy().astype(np.int64)                 # D integers: the size of `points`
-        off = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
-        out["off"] = torch.from_numpy(off).to(dev, non_blocking=True)
-        out["points"] = torch.empty((int(off[-1]), ps), dtype=torch.float32, device=dev)
-        if off[-1] > 0:
+        out["off"], out["points"] = _packed(counts, ps, dev)
+        if out["points"].shape[0] > 0:
             _native.check(L.fcn_refine_select_fill(*args, out["off"].data_ptr(), out["points"].data_ptr(),
                                                    _native.current_stream(dev)), "fcn_refine_select_fill")
     out["score"] = d8[:, 7].index_select(0, crow.to(torch.int64)) if D else d8[:0, 7]
     out["counts"] = counts
     return out
-
 
 
 def _candidates(who, frame_points, dets, cand_row, cand_frame):
@@ -170,9 +163,7 @@ def refine_training_candidates(frame_points, frame_off, dets, cand_row, cand_fra
         if len(kept) == 0:
             return {"kept": kept}
         seg_counts[drop] = 0
-        seg_off = np.concatenate([[0], np.cumsum(seg_counts.reshape(-1))]).astype(np.int64)
-        soff = torch.from_numpy(seg_off).to(dev, non_blocking=True)
-        points = torch.empty((int(seg_off[-1]), ps), dtype=torch.float32, device=dev)
+        soff, points = _packed(seg_counts, ps, dev)
         _native.check(L.fcn_refine_label_fill(*args, soff.data_ptr(), points.data_ptr(), _native.current_stream(dev)),
                       "fcn_refine_label_fill")
     idx = torch.from_numpy(kept).to(dev, non_blocking=True)
@@ -217,16 +208,12 @@ class RefineTrainSource:
 
     def __init__(self, frame_points, frame_off, dets, det_frame, det_types, gt_box3d, gt_off, builder, B, D, A, capacity, lpad,
                  seed, thresh=0.5, ratio=1.2, shift_ratio=0.05, pick=True, jitter=True):
-        from .inputs import DeviceDraws
         who = "RefineTrainSource"
         pts, foff, F, ps, S = _frames(who, frame_points, frame_off, resident=True)
         dev = frame_points.device
-        L = _native.lib()
-        if not (isinstance(dets, torch.Tensor) and dets.is_cuda and dets.dtype == torch.float32 and dets.is_contiguous()
-                and dets.dim() == 2 and dets.shape[1] == 8 and not dets.requires_grad):
-            raise ValueError("%s: dets must be a contiguous (R, 8) float32 device tensor (it is held, not copied)" % who)
+        resident.held(who, dets, "dets", "(R, 8)", lambda t: t.shape[1] == 8)
         R = int(dets.shape[0])
-        host = lambda a: (a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a))
+        host, up = resident.host, lambda x: resident.up(x, dev)
         dfr = np.ascontiguousarray(host(det_frame)).reshape(-1)
         types = [str(t) for t in det_types]
         if len(dfr) != R or len(types) != R:
@@ -249,9 +236,7 @@ class RefineTrainSource:
             if fixed.shape != (int(D), int(A), 7):
                 raise ValueError("%s: a jitter table must be (D, A, 7) = (%d, %d, 7), got %s" % (who, int(D), int(A), fixed.shape))
         B, D, A, capacity = int(B), int(D), int(A), int(capacity)
-        a, b = ctypes.c_int(0), ctypes.c_int(0)
-        _native.check(L.fcn_refine_train_plan_limits(ctypes.byref(a), ctypes.byref(b)), "fcn_refine_train_plan_limits")
-        max_u, max_segs = a.value, b.value
+        max_u, max_segs = self.limits()
         if not (1 <= A <= 64):
             raise ValueError("%s: A must lie in [1, 64], got %d" % (who, A))
         U = D * A
@@ -260,24 +245,19 @@ class RefineTrainSource:
                              (who, max_u, B, D, A, R))
         if U * S > max_segs:
             raise ValueError("%s: D * A * S = %d * %d segments exceed the plan's %d" % (who, U, S, max_segs))
-        if capacity < 1:
-            raise ValueError("%s: capacity must be >= 1 row, got %d" % (who, capacity))
+        resident.check_capacity(who, capacity)
         lpad = [int(x) for x in lpad]
         if len(lpad) != 4 or min(lpad) < 1:
             raise ValueError("%s: lpad must be four window counts >= 1, got %r" % (who, lpad))
         r = float(shift_ratio)
         if not (0.0 <= r < 1.0) or not (float(ratio) > 0.0):
             raise ValueError("%s: shift_ratio must lie in [0, 1) and ratio be positive, got %r, %r" % (who, shift_ratio, ratio))
-        if builder.device.type != "cuda":
-            raise RuntimeError("frustum_convnet_amd: input construction is a HIP kernel (MI355X only); no CPU fallback")
-        cls = [builder.classes.index(t) if t in builder.classes else -1 for t in types]
-        if min(cls) < 0:
-            raise ValueError("%s: type %r is not one of %r" % (who, types[cls.index(-1)], tuple(builder.classes)))
+        resident.need_device_builder(builder)
+        cls = resident.class_index(who, builder.classes, types)
         self.device, self.builder, self.lpad = dev, builder, lpad
         self.B, self.D, self.A, self.U, self.R, self.G, self.F, self.S, self.ps, self.capacity = B, D, A, U, R, G, F, S, ps, capacity
         self.pick, self.draw_jitter = bool(pick), fixed is None and bool(jitter)
         self.thresh, self.ratio, self.shift_ratio = float(thresh), float(ratio), r
-        up = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(dev)
         f64, i32, i64 = (dict(dtype=t, device=dev) for t in (torch.float64, torch.int32, torch.int64))
         N = builder.npoints
         # ---- resident: the frames, the detections (held), the labels
@@ -292,8 +272,9 @@ class RefineTrainSource:
         # ---- the generators
         seed = int(seed)
         self.draws_pick, self.draws_jitter, self.draws_sample = (DeviceDraws(seed + k, builder.device) for k in range(3))
-        self.status = torch.zeros((1,), **i32)
-        # ---- every intermediate
+        # ---- the batch and every intermediate
+        self.points, self.seg_off, self.off, self.counts, self.slot_unit, self.n_kept, self.status = \
+            resident.batch_skeleton(dev, B, U, S, capacity, ps, U)
         self.cand_row = torch.arange(D, **i32).view(1, D)
         self.pick_scalars = (torch.zeros((1,), **f64), torch.zeros((1,), **f64))
         self.cand_frame = torch.zeros((D,), **i32)
@@ -303,22 +284,15 @@ class RefineTrainSource:
         self.both = torch.zeros((2, U, S), **i32)               # selected, positive
         # the per-unit tables have U + 1 rows: row U is the spare entry an empty slot gathers -- a unit box at the origin, its
         # label box equal to the predicted one -- written here once and never by a kernel
-        hx, hz = np.asarray([1, 1, -1, -1, 1, 1, -1, -1]) * 0.5, np.asarray([1, -1, -1, 1, 1, -1, -1, 1]) * 0.5
-        hy = np.asarray([1, 1, 1, 1, -1, -1, -1, -1]) * 0.5
-        spare = torch.from_numpy(np.stack([hx, hy, hz], 1).reshape(24)).to(dev)
         self.pred_box3d, self.box3d = torch.zeros((U + 1, 24), **f64), torch.zeros((U + 1, 24), **f64)
         self.pred_angle, self.heading = torch.zeros((U + 1,), **f64), torch.zeros((U + 1,), **f64)
         self.pred_size, self.size = torch.zeros((U + 1, 3), **f64), torch.zeros((U + 1, 3), **f64)
         for tab in (self.pred_box3d, self.box3d):
-            tab[U] = spare
+            tab[U] = resident.spare_corners(dev)
         for tab in (self.pred_size, self.size):
             tab[U] = 1.0
-        self.slot_unit, self.slot_cand, self.n_kept = torch.full((B,), U, **i32), torch.full((B,), D, **i32), torch.zeros((1,), **i32)
+        self.slot_cand = torch.full((B,), D, **i32)
         self.unit_cand = torch.div(torch.arange(U + 1, **i32), A, rounding_mode="floor").to(torch.int32)     # row U -> D
-        self.seg_off, self.off = torch.zeros((U * S + 1,), **i64), torch.zeros((B + 1,), **i64)
-        self.counts = torch.zeros((B,), **i64)
-        # the spare row is what an empty slot's all-zero choice row reads: fcn_prepare_inputs_refine indexes off[b] + choice
-        self.points = torch.zeros((capacity + 1, ps), dtype=torch.float32, device=dev)
         self.t = {"raw": self.points, "off": self.off, "choice": torch.zeros((B, N), **i32),
                   "pcorners": torch.zeros((B, 24), **f64), "pangle": torch.zeros((B,), **f64), "psize": torch.zeros((B, 3), **f64),
                   "corners": torch.zeros((B, 24), **f64), "heading": torch.zeros((B,), **f64), "size": torch.zeros((B, 3), **f64),
@@ -333,9 +307,7 @@ class RefineTrainSource:
     @staticmethod
     def limits():
         """(the largest D * A, the largest D * A * S) of the plan."""
-        a, b = ctypes.c_int(0), ctypes.c_int(0)
-        _native.check(_native.lib().fcn_refine_train_plan_limits(ctypes.byref(a), ctypes.byref(b)), "fcn_refine_train_plan_limits")
-        return a.value, b.value
+        return resident.limits("fcn_refine_train_plan_limits", 2)
 
     def _gather_candidates(self):
         idx = self.cand_row.view(-1)
@@ -417,30 +389,23 @@ class CascadeLink:
 
     def __init__(self, stage1, stage2, refine_builder, frame_points, frame_off, B1, L2, G, top_k, D, B, capacity, lpad, seed, method,
                  thresh, ratio=1.2):
-        from .inputs import DeviceDraws
         who = "CascadeLink"
-        if not (isinstance(frame_points, torch.Tensor) and frame_points.is_cuda and frame_points.dtype == torch.float32 and
-                frame_points.is_contiguous() and frame_points.dim() == 2 and frame_points.shape[0] >= 1 and not frame_points.requires_grad):
-            raise ValueError("%s: frame_points must be a contiguous (n >= 1, >= 3) float32 device tensor (it is held, not copied)" % who)
+        resident.held(who, frame_points)
         pts, foff, F, ps, S = _frames(who, frame_points, frame_off, resident=True)
         dev = frame_points.device
         if stage1.training or stage2.training:
             raise ValueError("%s: both models must be in eval mode" % who)
         builder = refine_builder
-        if builder.device.type != "cuda":
-            raise RuntimeError("frustum_convnet_amd: input construction is a HIP kernel (MI355X only); no CPU fallback")
+        resident.need_device_builder(builder)
         B1, L2, G, top_k, D, B, capacity = (int(x) for x in (B1, L2, G, top_k, D, B, capacity))
         max_u, max_segs = RefineTrainSource.limits()
         if B1 < 1 or L2 < 1 or G < 1 or G > 65536:
             raise ValueError("%s: need B1 >= 1, L2 >= 1 and 1 <= G <= 65536, got B1 = %d, L2 = %d, G = %d" % (who, B1, L2, G))
         if not (1 <= top_k <= 4096):
             raise ValueError("%s: top_k must lie in [1, 4096] (the NMS sorts at most 4096 rows of a group), got %d" % (who, top_k))
-        if not (1 <= B <= D <= max_u):
-            raise ValueError("%s: need 1 <= B <= D <= %d, got B = %d, D = %d" % (who, max_u, B, D))
-        if D * S > max_segs:
-            raise ValueError("%s: D * S = %d * %d segments exceed the plan's %d" % (who, D, S, max_segs))
-        if capacity < 1:
-            raise ValueError("%s: capacity must be >= 1 row, got %d" % (who, capacity))
+        resident.check_slots(who, B, D, max_u)
+        resident.check_segments(who, D, S, max_segs)
+        resident.check_capacity(who, capacity)
         lpad = [int(x) for x in lpad]
         if len(lpad) != 4 or min(lpad) < 1:
             raise ValueError("%s: lpad must be four window counts >= 1, got %r" % (who, lpad))
@@ -454,7 +419,7 @@ class CascadeLink:
         self.device, self.stage1, self.stage2, self.builder, self.lpad = dev, stage1, stage2, builder, lpad
         self.B1, self.L2, self.G, self.top_k, self.D, self.B, self.F, self.S, self.ps = B1, L2, G, top_k, D, B, F, S, ps
         self.R, self.capacity, self.method, self.thresh, self.ratio = B1 * L2, capacity, method, float(thresh), float(ratio)
-        f32, f64, i32, i64 = (dict(dtype=t, device=dev) for t in (torch.float32, torch.float64, torch.int32, torch.int64))
+        f32, f64, i32 = (dict(dtype=t, device=dev) for t in (torch.float32, torch.float64, torch.int32))
         N, C = builder.npoints, len(builder.classes)
         # ---- resident: the frames (held) and the frustums' tables
         self.frames, self.frame_off = (pts, foff), foff
@@ -463,23 +428,18 @@ class CascadeLink:
         self.strides_c = (ctypes.c_double * 4)(*builder.strides)
         self.lpad_c = (ctypes.c_int32 * 4)(*lpad)
         self.draws = DeviceDraws(int(seed), builder.device)
-        self.status = torch.zeros((1,), **i32)
-        # ---- every intermediate.  The per-candidate tables have D + 1 rows: row D is the spare entry an empty slot gathers -- no
+        # ---- the batch and every intermediate.  The per-candidate tables have D + 1 rows: row D is the spare entry an empty slot gathers -- no
         # first-stage row, class 0, the spare group G, score 0, a unit box at the origin -- written here once and never by a kernel
+        self.points, self.seg_off, self.off, self.counts, self.slot_unit, self.n_kept, self.status = \
+            resident.batch_skeleton(dev, B, D, S, capacity, ps, D)
         self.cand_row, self.cand_frame = torch.full((D + 1,), -1, **i32), torch.full((D + 1,), -1, **i32)
         self.cand_class, self.cand_group = torch.zeros((D + 1,), **i32), torch.full((D + 1,), G, **i32)
         self.cand_score, self.n_cand = torch.zeros((D + 1, 1), **f32), torch.zeros((1,), **i32)
         self.seg_cnt = torch.zeros((D, S), **i32)
-        hx, hz = np.asarray([1, 1, -1, -1, 1, 1, -1, -1]) * 0.5, np.asarray([1, -1, -1, 1, 1, -1, -1, 1]) * 0.5
-        hy = np.asarray([1, 1, 1, 1, -1, -1, -1, -1]) * 0.5
         self.pred_box3d, self.pred_angle, self.pred_size = torch.zeros((D + 1, 24), **f64), torch.zeros((D + 1,), **f64), torch.zeros((D + 1, 3), **f64)
-        self.pred_box3d[D] = torch.from_numpy(np.stack([hx, hy, hz], 1).reshape(24)).to(dev)
+        self.pred_box3d[D] = resident.spare_corners(dev)
         self.pred_size[D] = 1.0
-        self.slot_unit, self.n_kept = torch.full((B,), D, **i32), torch.zeros((1,), **i32)
-        self.seg_off, self.off, self.counts = torch.zeros((D * S + 1,), **i64), torch.zeros((B + 1,), **i64), torch.zeros((B,), **i64)
         self.slot_class, self.slot_group, self.stage1_row = torch.zeros((B,), **i32), torch.full((B,), G, **i32), torch.full((B,), -1, **i32)
-        # the spare row is what an empty slot's all-zero choice row reads: fcn_prepare_inputs_refine indexes off[b] + choice
-        self.points = torch.zeros((capacity + 1, ps), **f32)
         self.t = {"raw": self.points, "off": self.off, "choice": torch.zeros((B, N), **i32),
                   "pcorners": torch.zeros((B, 24), **f64), "pangle": torch.zeros((B,), **f64), "psize": torch.zeros((B, 3), **f64),
                   "coin": torch.zeros((B,), **f64), "normal": torch.zeros((B,), **f64)}
@@ -501,13 +461,10 @@ class CascadeLink:
         types = [str(t) for t in types]
         if len(fr) != self.B1 or len(ug) != self.B1 or len(types) != self.B1:
             raise ValueError("%s: %d frustums, got %d frames, %d types, %d groups" % (who, self.B1, len(fr), len(types), len(ug)))
-        if fr.dtype.kind not in "iu" or ug.dtype.kind not in "iu" or fr.min() < 0 or fr.max() >= self.F or ug.min() < 0 or ug.max() >= self.G:
-            raise ValueError("%s: frames must be integers in [0, %d) and groups integers in [0, %d)" % (who, self.F, self.G))
-        cls = [self.builder.classes.index(t) if t in self.builder.classes else -1 for t in types]
-        if min(cls) < 0:
-            raise ValueError("%s: type %r is not one of %r" % (who, types[cls.index(-1)], tuple(self.builder.classes)))
+        resident.check_rows(who, fr, self.F, ug, self.G)
+        cls = resident.class_index(who, self.builder.classes, types)
         for dst, src in ((self.unit_frame, fr), (self.unit_class, cls), (self.unit_group, ug)):
-            dst.copy_(torch.from_numpy(np.ascontiguousarray(np.asarray(src, dtype=np.int32))))
+            dst.copy_(resident.up(np.asarray(src, dtype=np.int32)))
         return self
 
     def step(self, data_dicts):
@@ -583,7 +540,6 @@ class FrameCascade:
     def __init__(self, stage1, stage2, input_builder, refine_builder, frame_points, frame_off, calib, img_size, B1, D1, capacity1, G,
                  top_k, D, B, capacity, lpad, seed, method, thresh, ratio=1.2, clip_distance=2.0, clip_boxes=True,
                  img_height_threshold=5, lidar_point_threshold=1):
-        from .frustum import FrameDetectSource
         if tuple(input_builder.classes) != tuple(refine_builder.classes):
             raise ValueError("FrameCascade: the two builders must share their classes, got %r and %r" %
                              (tuple(input_builder.classes), tuple(refine_builder.classes)))

@@ -21,15 +21,18 @@ of slots and, when asked, the image-FOV search set of the second stage (fcn_frus
 fcn_frustum_fov_plan, csrc/frustum_detect_plan.h).  SunrgbdDetectSource is the SUN-RGBD inference path the same way, the frustum
 subsamples drawn on the device and every (frame, class) NMS group numbered by the plan (fcn_frustum_sunrgbd_detect_count / _plan /
 _fill, csrc/frustum_sunrgbd_detect_plan.h); evaluate.SunrgbdFrameChain carries it on to corners and scores.
-No CPU fallback.
+What the four sources do once on the host -- refusals, the label and detection tables, the batch skeleton -- is resident.py's, shared
+with cascade.py's two; a source states its own calibration, options, intermediates and step().  No CPU fallback.
 """
 import ctypes
 
 import numpy as np
 import torch
 
-from . import _native
+from . import _native, resident
 from .detect import _need_cuda
+from .inputs import DeviceDraws
+from .resident import DetectTable, LabelTable
 
 
 def _calib(calib, img_size, F, dev):
@@ -68,17 +71,31 @@ def _frames(who, frame_points, frame_off, resident=False):
     return pts, foff, F, ps, S
 
 
+def _boxes(who, boxes2d, box_frame, dev):
+    """The D 2-D boxes of a reading entry point and the frame of each, on the device: (D,4) fp64, (D) int32, D."""
+    boxes = torch.as_tensor(boxes2d).to(device=dev, dtype=torch.float64).contiguous().view(-1, 4)
+    bframe = torch.as_tensor(box_frame).to(device=dev, dtype=torch.int32).contiguous().view(-1)
+    D = int(bframe.numel())
+    if boxes.shape[0] != D:
+        raise ValueError("%s: %d boxes but %d frames" % (who, boxes.shape[0], D))
+    return boxes, bframe, D
+
+
+def _packed(seg_counts, ps, dev):
+    """Between the count and the fill of a reading entry point: from the (boxes, S) segment counts the host has just read, their
+    exclusive prefix sum on the device (one entry more: the total) and the point buffer it sizes."""
+    seg_off = np.concatenate([[0], np.cumsum(seg_counts.reshape(-1))]).astype(np.int64)
+    soff = torch.from_numpy(seg_off).to(dev, non_blocking=True)
+    return soff, torch.empty((int(seg_off[-1]), ps), dtype=torch.float32, device=dev)
+
+
 def _setup(who, frame_points, frame_off, calib, img_size, boxes2d, box_frame, clip_distance, clip_boxes):
     """The arguments both pairs of entry points share (fs_in of _native.py) from the Python-level inputs, the tensors that back
     them, and F, ps, D, S."""
     pts, foff, F, ps, S = _frames(who, frame_points, frame_off)
     dev = frame_points.device
     P, V2C, R0, wh = _calib(calib, img_size, F, dev)
-    boxes = torch.as_tensor(boxes2d).to(device=dev, dtype=torch.float64).contiguous().view(-1, 4)
-    bframe = torch.as_tensor(box_frame).to(device=dev, dtype=torch.int32).contiguous().view(-1)
-    D = int(bframe.numel())
-    if boxes.shape[0] != D:
-        raise ValueError("%s: %d boxes but %d frames" % (who, boxes.shape[0], D))
+    boxes, bframe, D = _boxes(who, boxes2d, box_frame, dev)
     args = (pts.data_ptr(), foff.data_ptr(), F, ps, P.data_ptr(), V2C.data_ptr(), R0.data_ptr(), wh.data_ptr(), boxes.data_ptr(),
             bframe.data_ptr(), D, S, 1 if clip_boxes else 0, float(clip_distance))
     return args, (pts, foff, P, V2C, R0, wh, boxes, bframe), ps, D, S
@@ -104,10 +121,8 @@ def frustum_candidates(frame_points, frame_off, calib, img_size, boxes2d, box_fr
         _native.check(L.fcn_frustum_select_count(*args, out["box2d"].data_ptr(), out["frustum_angle"].data_ptr(),
                                                  scnt.data_ptr(), _native.current_stream(dev)), "fcn_frustum_select_count")
         seg_counts = scnt.cpu().numpy().astype(np.int64)                    # D * S integers: the size of `points`
-        seg_off = np.concatenate([[0], np.cumsum(seg_counts.reshape(-1))]).astype(np.int64)
-        soff = torch.from_numpy(seg_off).to(dev, non_blocking=True)
-        out["points"] = torch.empty((int(seg_off[-1]), ps), dtype=torch.float32, device=dev)
-        if seg_off[-1] > 0:
+        soff, out["points"] = _packed(seg_counts, ps, dev)
+        if out["points"].shape[0] > 0:
             _native.check(L.fcn_frustum_select_fill(*args, soff.data_ptr(), out["points"].data_ptr(),
                                                     _native.current_stream(dev)), "fcn_frustum_select_fill")
     out["off"] = soff[::S].contiguous()                                     # every S-th entry is a box's offset
@@ -206,11 +221,8 @@ def frustum_training_candidates(frame_points, frame_off, calib, img_size, boxes2
         if len(kept) == 0:
             return {"kept": kept}
         seg_counts[drop] = 0
-        seg_off = np.concatenate([[0], np.cumsum(seg_counts.reshape(-1))]).astype(np.int64)
-        soff = torch.from_numpy(seg_off).to(dev, non_blocking=True)
-        total = int(seg_off[-1])
-        points = torch.empty((total, ps), dtype=torch.float32, device=dev)
-        seg = torch.empty((total,), dtype=torch.int64, device=dev)
+        soff, points = _packed(seg_counts, ps, dev)
+        seg = torch.empty((points.shape[0],), dtype=torch.int64, device=dev)
         _native.check(L.fcn_frustum_label_fill(*args, gt.data_ptr(), soff.data_ptr(), points.data_ptr(), seg.data_ptr(),
                                                _native.current_stream(dev)), "fcn_frustum_label_fill")
     idx = torch.from_numpy(kept).to(dev, non_blocking=True)
@@ -281,17 +293,8 @@ def _setup_sunrgbd(who, frame_points, frame_off, K, Rtilt, boxes2d, box_frame):
     """The arguments the four entry points share (sr_in of _native.py), the tensors that back them, and ps, D, S."""
     pts, foff, F, ps, S = _frames(who, frame_points, frame_off)
     dev = frame_points.device
-    cal = []
-    for name, m in (("K", K), ("Rtilt", Rtilt)):
-        t = torch.as_tensor(m).to(device=dev, dtype=torch.float64).contiguous()
-        if t.numel() != F * 9:
-            raise ValueError("%s: %s must hold %d x 9 numbers, got %s" % (who, name, F, tuple(t.shape)))
-        cal.append(t.view(F, 9))
-    boxes = torch.as_tensor(boxes2d).to(device=dev, dtype=torch.float64).contiguous().view(-1, 4)
-    bframe = torch.as_tensor(box_frame).to(device=dev, dtype=torch.int32).contiguous().view(-1)
-    D = int(bframe.numel())
-    if boxes.shape[0] != D:
-        raise ValueError("%s: %d boxes but %d frames" % (who, boxes.shape[0], D))
+    cal = resident.intrinsics(who, K, Rtilt, F, dev)
+    boxes, bframe, D = _boxes(who, boxes2d, box_frame, dev)
     args = (pts.data_ptr(), foff.data_ptr(), F, ps, cal[0].data_ptr(), cal[1].data_ptr(), boxes.data_ptr(), bframe.data_ptr(), D, S)
     return args, (pts, foff, cal[0], cal[1], boxes, bframe), ps, D, S
 
@@ -319,10 +322,8 @@ def sunrgbd_candidates(frame_points, frame_off, K, Rtilt, boxes2d, box_frame, su
         seg_counts = scnt.cpu().numpy().astype(np.int64)                    # D * S integers: the size of `points`
         counts = seg_counts.sum(1)
         sub = draw_frustum_subsample(counts, cap, rng) if sub is None else _check_sub(who, sub, counts)
-        seg_off = np.concatenate([[0], np.cumsum(seg_counts.reshape(-1))]).astype(np.int64)
-        soff = torch.from_numpy(seg_off).to(dev, non_blocking=True)
-        out["points"] = torch.empty((int(seg_off[-1]), ps), dtype=torch.float32, device=dev)
-        if seg_off[-1] > 0:
+        soff, out["points"] = _packed(seg_counts, ps, dev)
+        if out["points"].shape[0] > 0:
             _native.check(L.fcn_frustum_sunrgbd_fill(*args, soff.data_ptr(), out["points"].data_ptr(),
                                                      _native.current_stream(dev)), "fcn_frustum_sunrgbd_fill")
     out["off"] = soff[::S].contiguous()                                     # every S-th entry is a box's offset
@@ -375,11 +376,8 @@ def sunrgbd_training_candidates(frame_points, frame_off, K, Rtilt, boxes2d, box_
         if len(kept) == 0:
             return {"kept": kept}
         seg_counts[drop] = 0
-        seg_off = np.concatenate([[0], np.cumsum(seg_counts.reshape(-1))]).astype(np.int64)
-        soff = torch.from_numpy(seg_off).to(dev, non_blocking=True)
-        total = int(seg_off[-1])
-        points = torch.empty((total, ps), dtype=torch.float32, device=dev)
-        seg = torch.empty((total,), dtype=torch.int64, device=dev)
+        soff, points = _packed(seg_counts, ps, dev)
+        seg = torch.empty((points.shape[0],), dtype=torch.int64, device=dev)
         _native.check(L.fcn_frustum_sunrgbd_label_fill(*args, gt.data_ptr(), soff.data_ptr(), points.data_ptr(), seg.data_ptr(),
                                                        _native.current_stream(dev)), "fcn_frustum_sunrgbd_label_fill")
         idx = torch.from_numpy(kept).to(dev, non_blocking=True)
@@ -447,91 +445,39 @@ class FrameTrainSource:
 
     def __init__(self, frame_points, frame_off, calib, img_size, gt_box2d, gt_box3d, box_frame, types, builder, B, D, capacity,
                  seed, perturb=True, pick=True, shift_ratio=0.1, min_box_height=25.0, clip_distance=2.0, select_box2d=None):
-        from .inputs import DeviceDraws
         who = "FrameTrainSource"
         pts, foff, F, ps, S = _frames(who, frame_points, frame_off, resident=True)
         dev = frame_points.device
-        L = _native.lib()
         P, V2C, R0, wh = _calib(calib, img_size, F, dev)
-        host = lambda a: (a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a))
-        gt2d = np.ascontiguousarray(host(gt_box2d), dtype=np.float64).reshape(-1, 4)
-        gt3d = np.ascontiguousarray(host(gt_box3d), dtype=np.float64).reshape(-1, 7)
-        bf = np.ascontiguousarray(host(box_frame)).reshape(-1)
-        G = len(bf)
-        types = [str(t) for t in types]
-        if len(gt2d) != G or len(gt3d) != G or len(types) != G:
-            raise ValueError("%s: %d box_frame, %d gt_box2d, %d gt_box3d, %d types" % (who, G, len(gt2d), len(gt3d), len(types)))
-        if bf.dtype.kind not in "iu" or G == 0 or int(bf.min()) < 0 or int(bf.max()) >= F:
-            raise ValueError("%s: box_frame must hold integers in [0, %d)" % (who, F))
-        B, D, capacity = int(B), int(D), int(capacity)
-        a, b = ctypes.c_int(0), ctypes.c_int(0)
-        _native.check(L.fcn_frustum_train_plan_limits(ctypes.byref(a), ctypes.byref(b)), "fcn_frustum_train_plan_limits")
-        max_d, max_segs = a.value, b.value
-        if not (1 <= B <= D <= G) or D > max_d:
-            raise ValueError("%s: need 1 <= B <= D <= G and D <= %d, got B = %d, D = %d, G = %d" % (who, max_d, B, D, G))
-        if D * S > max_segs:
-            raise ValueError("%s: D * S = %d * %d segments exceed the plan's %d" % (who, D, S, max_segs))
-        if capacity < 1:
-            raise ValueError("%s: capacity must be >= 1 row, got %d" % (who, capacity))
+        lab = self.labels = LabelTable(who, gt_box2d, gt_box3d, box_frame, types, F)
+        B, D, G, capacity = int(B), int(D), lab.G, int(capacity)
+        max_d, max_segs = resident.limits("fcn_frustum_train_plan_limits", 2)
+        resident.check_slots(who, B, D, max_d, G)
+        resident.check_segments(who, D, S, max_segs)
+        resident.check_capacity(who, capacity)
         r = float(shift_ratio)
         if not (0.0 <= r < 1.0):
             raise ValueError("%s: shift_ratio must lie in [0, 1), got %r" % (who, shift_ratio))
-        bad = np.nonzero(~((gt2d[:, 0] < gt2d[:, 2]) & (gt2d[:, 1] < gt2d[:, 3])))[0]
-        if len(bad):
-            raise ValueError("%s: label box %d is degenerate: %r" % (who, bad[0], tuple(gt2d[bad[0]])))
-        wh_h = wh.cpu().numpy()[bf]
-        if perturb:                                             # perturb_boxes2d's second refusal, vectorised
-            if select_box2d is not None:
-                raise ValueError("%s: select_box2d goes with perturb=False" % who)
-            w, h = gt2d[:, 2] - gt2d[:, 0], gt2d[:, 3] - gt2d[:, 1]
-            cx, cy = (gt2d[:, 0] + gt2d[:, 2]) / 2.0, (gt2d[:, 1] + gt2d[:, 3]) / 2.0
-            rx, ry = w * r + w * (1 + r) / 2.0, h * r + h * (1 + r) / 2.0
-            bad = np.nonzero(~((cx - rx < wh_h[:, 0] - 1) & (cx + rx > 0) & (cy - ry < wh_h[:, 1] - 1) & (cy + ry > 0)))[0]
-            if len(bad):
-                raise ValueError("%s: label box %d cannot be perturbed into the %g x %g image: %r" %
-                                 (who, bad[0], wh_h[bad[0], 0], wh_h[bad[0], 1], tuple(gt2d[bad[0]])))
-        sel2d = gt2d if select_box2d is None else np.ascontiguousarray(host(select_box2d), dtype=np.float64).reshape(-1, 4)
-        if len(sel2d) != G:
-            raise ValueError("%s: %d select_box2d for %d labels" % (who, len(sel2d), G))
-        if builder.device.type != "cuda":
-            raise RuntimeError("frustum_convnet_amd: input construction is a HIP kernel (MI355X only); no CPU fallback")
-        cls = [builder.classes.index(t) if t in builder.classes else -1 for t in types]
-        if min(cls) < 0:
-            raise ValueError("%s: type %r is not one of %r" % (who, types[cls.index(-1)], tuple(builder.classes)))
         self.device, self.builder = dev, builder
         self.B, self.D, self.G, self.F, self.S, self.ps, self.capacity = B, D, G, F, S, ps, capacity
         self.perturb, self.pick, self.shift_ratio = bool(perturb), bool(pick), r
         self.min_box_height, self.clip_distance = float(min_box_height), float(clip_distance)
-        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
         f64, i32, i64 = (dict(dtype=t, device=dev) for t in (torch.float64, torch.int32, torch.int64))
         N = builder.npoints
-        # ---- resident: the frames, the per-label tensors
+        # ---- resident: the frames, the label table (the perturbation clips to the image: wh), the generators
         self.frames = (pts, foff, P, V2C, R0, wh)
-        self.g_box2d, self.g_sel2d, self.g_box3d, self.g_frame = up(gt2d), up(sel2d), up(gt3d), up(bf.astype(np.int32))
-        self.g_heading, self.g_size = self.g_box3d[:, 6].contiguous(), self.g_box3d[:, 3:6].contiguous()
+        resident.adopt(self, lab.load(builder, dev, D, self.perturb, select_box2d, r, wh.cpu().numpy()))
+        self.g_size = self.g_box3d[:, 3:6].contiguous()
         self.g_P = P.index_select(0, self.g_frame.to(torch.int64)).contiguous()
-        self.g_class = up(np.asarray(cls, dtype=np.int64).reshape(G, 1))
-        self.eye = torch.eye(len(builder.classes), dtype=torch.float32, device=dev)
-        self.g_count = torch.full((1,), G, **i64)
-        # ---- the generators
         seed = int(seed)
         self.draws_pick, self.draws_box, self.draws_sample = (DeviceDraws(seed + k, builder.device) for k in range(3))
-        self.status = torch.zeros((1,), **i32)
-        # ---- every intermediate
-        self.pick_idx = torch.arange(D, **i32).view(1, D)
-        self.pick_scalars = (torch.zeros((1,), **f64), torch.zeros((1,), **f64))
-        self.gt2d, self.sel2d, self.gt3d = torch.zeros((D, 4), **f64), torch.zeros((D, 4), **f64), torch.zeros((D, 7), **f64)
-        self.bframe = torch.zeros((D,), **i32)
-        self.boxes = torch.zeros((D, 4), **f64) if self.perturb else self.sel2d       # the boxes that select (perturbed or plain)
+        # ---- the batch and every intermediate
+        self.points, self.seg_off, self.off, self.counts, self.slot_box, self.n_kept, self.status = \
+            resident.batch_skeleton(dev, B, D, S, capacity, ps, 0)
         self.box2d, self.angle, self.corners = torch.zeros((D, 4), **f64), torch.zeros((D,), **f64), torch.zeros((D, 24), **f64)
         self.both = torch.zeros((2, D, S), **i32)               # selected, positive
-        self.slot_box, self.n_kept = torch.zeros((B,), **i32), torch.zeros((1,), **i32)
-        self.seg_off, self.off = torch.zeros((D * S + 1,), **i64), torch.zeros((B + 1,), **i64)
-        # the spare row is what an empty slot's all-zero choice row reads: fcn_prepare_inputs indexes off[b] + choice
-        self.points = torch.zeros((capacity + 1, ps), dtype=torch.float32, device=dev)
         self.seg = torch.zeros((capacity + 1,), **i64)
         self.slot_label = torch.zeros((B,), **i32)
-        self.counts = torch.zeros((B,), **i64)
         self.t = {"raw": self.points, "off": self.off, "seg": self.seg, "choice": torch.zeros((B, N), **i32),
                   "fangle": torch.zeros((B,), **f64), "box2d": torch.zeros((B, 4), **f64), "P": torch.zeros((B, 12), **f64),
                   "corners": torch.zeros((B, 24), **f64), "heading": torch.zeros((B,), **f64), "size": torch.zeros((B, 3), **f64),
@@ -541,21 +487,18 @@ class FrameTrainSource:
             self.t["one_hot"] = torch.zeros((B, len(builder.classes)), dtype=torch.float32, device=dev)
         self.out = builder.alloc(B)
         if not self.pick:                                       # the first D labels, gathered once
-            self._gather_labels()
+            lab._gather_labels()
 
     @staticmethod
     def limits():
         """(the attempt cap of the perturbation, the largest D, the largest D * S) of the kernels."""
-        a, b, c = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
-        L = _native.lib()
-        _native.check(L.fcn_box2d_perturb_limits(ctypes.byref(a)), "fcn_box2d_perturb_limits")
-        _native.check(L.fcn_frustum_train_plan_limits(ctypes.byref(b), ctypes.byref(c)), "fcn_frustum_train_plan_limits")
-        return a.value, b.value, c.value
+        return resident.limits("fcn_box2d_perturb_limits", 1) + resident.limits("fcn_frustum_train_plan_limits", 2)
 
-    def _gather_labels(self):
-        idx = self.pick_idx.view(-1)
-        for src, dst in ((self.g_box2d, self.gt2d), (self.g_sel2d, self.sel2d), (self.g_box3d, self.gt3d), (self.g_frame, self.bframe)):
-            torch.index_select(src, 0, idx, out=dst)
+    def _advance_pick(self):                                    # (the three step counters stay equal)
+        p = lambda x: x.data_ptr()
+        _native.check(_native.lib().fcn_box2d_perturb(p(self.gt2d), p(self.bframe), p(self.frames[5]), 0, self.F, self.shift_ratio,
+                                                      self.draws_pick.seed, p(self.draws_pick.state), 1, p(self.gt2d), p(self.status),
+                                                      _native.current_stream(self.device)), "fcn_box2d_perturb")
 
     def step(self):
         """Enqueues one batch on the current stream -- pick, gather, perturb, count, plan, fill, gather, draw, fcn_prepare_inputs --
@@ -568,13 +511,7 @@ class FrameTrainSource:
         pts, foff, P, V2C, R0, wh = self.frames
         with torch.cuda.device(dev):
             s = _native.current_stream(dev)
-            if self.pick:
-                self.draws_pick.draw(self.g_count, D, False, False, out=(self.pick_idx,) + self.pick_scalars)
-                self._gather_labels()
-            else:                                               # (the three step counters stay equal)
-                _native.check(L.fcn_box2d_perturb(p(self.gt2d), p(self.bframe), p(wh), 0, self.F, self.shift_ratio,
-                                                  self.draws_pick.seed, p(self.draws_pick.state), 1, p(self.gt2d), p(self.status), s),
-                              "fcn_box2d_perturb")
+            self.labels.pick(self.draws_pick, self.pick, self._advance_pick)
             _native.check(L.fcn_box2d_perturb(p(self.gt2d), p(self.bframe), p(wh), D if self.perturb else 0, self.F, self.shift_ratio,
                                               self.draws_box.seed, p(self.draws_box.state), 1, p(self.boxes), p(self.status), s),
                           "fcn_box2d_perturb")
@@ -630,92 +567,51 @@ class SunrgbdTrainSource:
 
     def __init__(self, frame_points, frame_off, K, Rtilt, gt_box2d, gt_box3d, box_frame, types, builder, B, D, capacity, seed,
                  perturb=True, pick=True, shift_ratio=0.1, cap=SUNRGBD_CAP, min_positives=SUNRGBD_MIN, select_box2d=None, sub=None):
-        from .inputs import DeviceDraws
         who = "SunrgbdTrainSource"
         pts, foff, F, ps, S = _frames(who, frame_points, frame_off, resident=True)
         dev = frame_points.device
         L = _native.lib()
-        cal = []
-        for name, m in (("K", K), ("Rtilt", Rtilt)):
-            t = torch.as_tensor(m).to(device=dev, dtype=torch.float64).contiguous()
-            if t.numel() != F * 9:
-                raise ValueError("%s: %s must hold %d x 9 numbers, got %s" % (who, name, F, tuple(t.shape)))
-            cal.append(t.view(F, 9))
-        host = lambda a: (a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a))
-        gt2d = np.ascontiguousarray(host(gt_box2d), dtype=np.float64).reshape(-1, 4)
-        gt3d = np.ascontiguousarray(host(gt_box3d), dtype=np.float64).reshape(-1, 7)
-        bf = np.ascontiguousarray(host(box_frame)).reshape(-1)
-        G = len(bf)
-        types = [str(t) for t in types]
-        if len(gt2d) != G or len(gt3d) != G or len(types) != G:
-            raise ValueError("%s: %d box_frame, %d gt_box2d, %d gt_box3d, %d types" % (who, G, len(gt2d), len(gt3d), len(types)))
-        if bf.dtype.kind not in "iu" or G == 0 or int(bf.min()) < 0 or int(bf.max()) >= F:
-            raise ValueError("%s: box_frame must hold integers in [0, %d)" % (who, F))
-        B, D, capacity, cap, min_positives = int(B), int(D), int(capacity), int(cap), int(min_positives)
+        cal = resident.intrinsics(who, K, Rtilt, F, dev)
+        lab = self.labels = LabelTable(who, gt_box2d, gt_box3d, box_frame, types, F)
+        B, D, G, capacity, cap, min_positives = int(B), int(D), lab.G, int(capacity), int(cap), int(min_positives)
         max_d, max_segs, max_cap = self.limits()
-        if not (1 <= B <= D <= G) or D > max_d:
-            raise ValueError("%s: need 1 <= B <= D <= G and D <= %d, got B = %d, D = %d, G = %d" % (who, max_d, B, D, G))
-        if D * S > max_segs:
-            raise ValueError("%s: D * S = %d * %d segments exceed the plan's %d" % (who, D, S, max_segs))
+        resident.check_slots(who, B, D, max_d, G)
+        resident.check_segments(who, D, S, max_segs)
         if not (1 <= cap <= max_cap):
             raise ValueError("%s: cap must lie in [1, %d], got %d" % (who, max_cap, cap))
-        if capacity < 1:
-            raise ValueError("%s: capacity must be >= 1 row, got %d" % (who, capacity))
+        resident.check_capacity(who, capacity)
         r = float(shift_ratio)
         if not (0.0 <= r < 1.0):
             raise ValueError("%s: shift_ratio must lie in [0, 1), got %r" % (who, shift_ratio))
-        if perturb and select_box2d is not None:
-            raise ValueError("%s: select_box2d goes with perturb=False" % who)
-        if sub is not None and (perturb or pick):
+        if sub is not None and (perturb or pick) and not (perturb and select_box2d is not None):   # (that refusal of load() comes first)
             raise ValueError("%s: sub goes with perturb=False and pick=False" % who)
-        sel2d = gt2d if select_box2d is None else np.ascontiguousarray(host(select_box2d), dtype=np.float64).reshape(-1, 4)
-        if len(sel2d) != G:
-            raise ValueError("%s: %d select_box2d for %d labels" % (who, len(sel2d), G))
-        if builder.device.type != "cuda":
-            raise RuntimeError("frustum_convnet_amd: input construction is a HIP kernel (MI355X only); no CPU fallback")
-        cls = [builder.classes.index(t) if t in builder.classes else -1 for t in types]
-        if min(cls) < 0:
-            raise ValueError("%s: type %r is not one of %r" % (who, types[cls.index(-1)], tuple(builder.classes)))
         self.device, self.builder = dev, builder
         self.B, self.D, self.G, self.F, self.S, self.ps, self.capacity = B, D, G, F, S, ps, capacity
         self.perturb, self.pick, self.shift_ratio, self.cap, self.min_positives = bool(perturb), bool(pick), r, cap, min_positives
-        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
         f64, i32, i64 = (dict(dtype=t, device=dev) for t in (torch.float64, torch.int32, torch.int64))
         N = builder.npoints
-        # ---- resident: the frames, the per-label tensors
+        # ---- resident: the frames, the label table (no clip: nothing of the boxes to refuse), the generators
         self.frames = (pts, foff, cal[0], cal[1])
-        self.g_box2d, self.g_sel2d, self.g_box3d, self.g_frame = up(gt2d), up(sel2d), up(gt3d), up(bf.astype(np.int32))
-        self.g_heading = self.g_box3d[:, 6].contiguous()
+        resident.adopt(self, lab.load(builder, dev, D, self.perturb, select_box2d))
         self.g_size = (self.g_box3d[:, 3:6] * 2.0).contiguous()                 # box3d_size = 2l, 2w, 2h
         self.g_K = cal[0].index_select(0, self.g_frame.to(torch.int64)).contiguous()
         self.g_R = cal[1].index_select(0, self.g_frame.to(torch.int64)).contiguous()
-        self.g_class = up(np.asarray(cls, dtype=np.int64).reshape(G, 1))
-        self.eye = torch.eye(len(builder.classes), dtype=torch.float32, device=dev)
-        self.g_count = torch.full((1,), G, **i64)
-        # ---- the generators
         seed = int(seed)
         self.draws_pick, self.draws_box, self.draws_sample, self.draws_sub = (DeviceDraws(seed + k, builder.device) for k in range(4))
-        self.status = torch.zeros((1,), **i32)
-        # ---- every intermediate
-        self.pick_idx = torch.arange(D, **i32).view(1, D)
-        self.pick_scalars = (torch.zeros((1,), **f64), torch.zeros((1,), **f64))
-        self.gt2d, self.sel2d, self.gt3d = torch.zeros((D, 4), **f64), torch.zeros((D, 4), **f64), torch.zeros((D, 7), **f64)
-        self.bframe = torch.zeros((D,), **i32)
-        self.boxes = torch.zeros((D, 4), **f64) if self.perturb else self.sel2d       # the boxes that select (perturbed or plain)
+        # ---- the batch and every intermediate.  off holds B starts, not B + 1 bounds: a slot's rows are off[b] ... + counts[b]
+        self.points, self.seg_off, _, self.counts, self.slot_box, self.n_kept, self.status = \
+            resident.batch_skeleton(dev, B, D, S, capacity, ps, 0)
+        self.off = torch.zeros((B,), **i64)
         self.box32, self.box64 = torch.zeros((D, 4), dtype=torch.float32, device=dev), torch.zeros((D, 4), **f64)
         self.angle, self.corners = torch.zeros((D,), **f64), torch.zeros((D, 24), **f64)
         self.both = torch.zeros((2, D, S), **i32)               # selected, positive
-        self.seg_off, self.row0 = torch.zeros((D * S + 1,), **i64), torch.zeros((D,), **i64)
+        self.row0 = torch.zeros((D,), **i64)
         self.cnt_stored, self.pos = torch.zeros((D,), **i32), torch.zeros((D,), **i32)
         self.plan_sub_off = torch.zeros((D + 1,), **i64)
         self.sub_off, self.sub = self.plan_sub_off, torch.zeros((D * cap,), **i32)
         self.fixed_sub = sub is not None
-        # the spare row is what an empty slot's all-zero choice row reads: fcn_prepare_inputs_sunrgbd indexes off[b] + choice
-        self.points = torch.zeros((capacity + 1, ps), dtype=torch.float32, device=dev)
         self.seg = torch.zeros((capacity + 1,), **i64)
-        self.slot_box, self.n_kept, self.slot_label = torch.zeros((B,), **i32), torch.zeros((1,), **i32), torch.zeros((B,), **i32)
-        self.off, self.counts, self.sub_start = torch.zeros((B,), **i64), torch.zeros((B,), **i64), torch.zeros((B,), **i64)
-        self.sub_len = torch.zeros((B,), **i32)
+        self.slot_label, self.sub_start, self.sub_len = torch.zeros((B,), **i32), torch.zeros((B,), **i64), torch.zeros((B,), **i32)
         self.t = {"raw": self.points, "off": self.off, "seg": self.seg, "choice": torch.zeros((B, N), **i32),
                   "fangle": torch.zeros((B,), **f64), "box2d": torch.zeros((B, 4), **f64), "K": torch.zeros((B, 9), **f64),
                   "R": torch.zeros((B, 9), **f64), "corners": torch.zeros((B, 24), **f64), "heading": torch.zeros((B,), **f64),
@@ -725,8 +621,8 @@ class SunrgbdTrainSource:
             self.t["one_hot"] = torch.zeros((B, len(builder.classes)), dtype=torch.float32, device=dev)
         self.out = builder.alloc(B)
         if not self.pick:                                       # the first D labels, gathered once
-            self._gather_labels()
-        if self.fixed_sub:                                      # one count launch, read once: what the table is checked against
+            lab._gather_labels()
+        if self.fixed_sub:                                     # one count launch, read once: what the table is checked against
             with torch.cuda.device(dev):
                 _native.check(L.fcn_frustum_sunrgbd_train_count(*self._args(), self.angle.data_ptr(), self.both[0].data_ptr(),
                                                                 self.both[1].data_ptr(), self.corners.data_ptr(),
@@ -739,22 +635,19 @@ class SunrgbdTrainSource:
                 raise ValueError("%s: sub needs a capacity that holds every row of the pre-kept boxes: %d > %d" % (who, rows, capacity))
             lens = [0 if ix is None else len(ix) for ix in sub]
             flat = [ix for ix in sub if ix is not None]
-            self.sub_off = up(np.concatenate([[0], np.cumsum(lens)]).astype(np.int64))
-            self.sub = up(np.concatenate(flat).astype(np.int32)) if flat else torch.zeros((1,), **i32)
+            self.sub_off = resident.up(np.concatenate([[0], np.cumsum(lens)]).astype(np.int64), dev)
+            self.sub = resident.up(np.concatenate(flat).astype(np.int32), dev) if flat else torch.zeros((1,), **i32)
 
     @staticmethod
     def limits():
         """(the largest D, the largest D * S, the largest cap) of the kernels."""
-        a, b, c, d = (ctypes.c_int(0) for _ in range(4))
-        L = _native.lib()
-        _native.check(L.fcn_frustum_train_plan_limits(ctypes.byref(a), ctypes.byref(b)), "fcn_frustum_train_plan_limits")
-        _native.check(L.fcn_draw_limits(ctypes.byref(c), ctypes.byref(d)), "fcn_draw_limits")
-        return a.value, b.value, c.value
+        return resident.limits("fcn_frustum_train_plan_limits", 2) + resident.limits("fcn_draw_limits", 2)[:1]
 
-    def _gather_labels(self):
-        idx = self.pick_idx.view(-1)
-        for src, dst in ((self.g_box2d, self.gt2d), (self.g_sel2d, self.sel2d), (self.g_box3d, self.gt3d), (self.g_frame, self.bframe)):
-            torch.index_select(src, 0, idx, out=dst)
+    def _advance_pick(self):                                    # (the four step counters stay equal)
+        p = lambda x: x.data_ptr()
+        _native.check(_native.lib().fcn_box2d_perturb_sunrgbd(p(self.gt2d), 0, self.shift_ratio, self.draws_pick.seed,
+                                                              p(self.draws_pick.state), 1, p(self.gt2d),
+                                                              _native.current_stream(self.device)), "fcn_box2d_perturb_sunrgbd")
 
     def _args(self):
         pts, foff, K, R = self.frames
@@ -772,12 +665,7 @@ class SunrgbdTrainSource:
         p = lambda x: x.data_ptr()
         with torch.cuda.device(dev):
             s = _native.current_stream(dev)
-            if self.pick:
-                self.draws_pick.draw(self.g_count, D, False, False, out=(self.pick_idx,) + self.pick_scalars)
-                self._gather_labels()
-            else:                                               # (the four step counters stay equal)
-                _native.check(L.fcn_box2d_perturb_sunrgbd(p(self.gt2d), 0, self.shift_ratio, self.draws_pick.seed,
-                                                          p(self.draws_pick.state), 1, p(self.gt2d), s), "fcn_box2d_perturb_sunrgbd")
+            self.labels.pick(self.draws_pick, self.pick, self._advance_pick)
             _native.check(L.fcn_box2d_perturb_sunrgbd(p(self.gt2d), D if self.perturb else 0, self.shift_ratio, self.draws_box.seed,
                                                       p(self.draws_box.state), 1, p(self.boxes), s), "fcn_box2d_perturb_sunrgbd")
             args = self._args()
@@ -845,24 +733,18 @@ class FrameDetectSource:
 
     def __init__(self, frame_points, frame_off, calib, img_size, builder, B1, D, capacity, seed, spare_group, clip_distance=2.0,
                  clip_boxes=True, img_height_threshold=5, lidar_point_threshold=1, fov=False):
-        from .inputs import DeviceDraws
         who = "FrameDetectSource"
-        if not (isinstance(frame_points, torch.Tensor) and frame_points.is_cuda and frame_points.dtype == torch.float32 and
-                frame_points.is_contiguous() and frame_points.dim() == 2 and frame_points.shape[0] >= 1 and not frame_points.requires_grad):
-            raise ValueError("%s: frame_points must be a contiguous (n >= 1, >= 3) float32 device tensor (it is held, not copied)" % who)
+        resident.held(who, frame_points)
         pts, foff, F, ps, S = _frames(who, frame_points, frame_off, resident=True)
         dev = frame_points.device
         P, V2C, R0, wh = _calib(calib, img_size, F, dev)
-        if builder.device.type != "cuda":
-            raise RuntimeError("frustum_convnet_amd: input construction is a HIP kernel (MI355X only); no CPU fallback")
+        resident.need_device_builder(builder)
         B1, D, capacity, spare_group = int(B1), int(D), int(capacity), int(spare_group)
         max_d, max_segs = self.limits()
-        if not (1 <= B1 <= D <= max_d):
-            raise ValueError("%s: need 1 <= B1 <= D <= %d, got B1 = %d, D = %d" % (who, max_d, B1, D))
+        resident.check_slots(who, B1, D, max_d, b="B1")
         if D * S > max_segs or (fov and F * S > max_segs):
             raise ValueError("%s: D * S = %d * %d (fov: F * S = %d * %d) segments exceed the plan's %d" % (who, D, S, F, S, max_segs))
-        if capacity < 1:
-            raise ValueError("%s: capacity must be >= 1 row, got %d" % (who, capacity))
+        resident.check_capacity(who, capacity)
         if not (0 <= spare_group < 2 ** 31):
             raise ValueError("%s: spare_group must be a non-negative int32, got %d" % (who, spare_group))
         hthr, pthr, clipd = float(img_height_threshold), float(lidar_point_threshold), float(clip_distance)
@@ -877,25 +759,19 @@ class FrameDetectSource:
         N, C = builder.npoints, len(builder.classes)
         # ---- resident: the frames (held), the calibration, the detection table with its spare row D
         self.frames = (pts, foff, P, V2C, R0, wh)
-        self.boxes2d = torch.zeros((D + 1, 4), **f64)
-        self.boxes2d[D] = torch.tensor([0.0, 0.0, 1.0, 1.0], **f64)
-        self.box_frame, self.box_class = torch.zeros((D + 1,), **i32), torch.zeros((D + 1,), **i32)
-        self.box_group, self.box_prob = torch.full((D + 1,), spare_group, **i32), torch.zeros((D + 1,), **f32)
-        self.n_boxes = torch.zeros((1,), **i32)
+        self.table = DetectTable(dev, D, F, builder.classes, spare_group)
+        resident.adopt(self, self.table)
         self.eye = torch.eye(C, **f32)
         self.draws = DeviceDraws(int(seed), builder.device)
-        self.status = torch.zeros((1,), **i32)
-        # ---- every intermediate.  The per-box outputs of the count have D + 1 rows as well: row D is what an empty slot gathers,
-        # the spare row's own box and a zero angle, written here once and never by a kernel
+        # ---- the batch and every intermediate.  The per-box outputs of the count have D + 1 rows as well: row D is what an empty
+        # slot gathers, the spare row's own box and a zero angle, written here once and never by a kernel
+        self.points, self.seg_off, self.off, self.counts, self.slot_box, self.n_kept, self.status = \
+            resident.batch_skeleton(dev, B1, D, S, capacity, ps, D)
         self.box2d, self.angle = torch.zeros((D + 1, 4), **f64), torch.zeros((D + 1,), **f64)
         self.box2d[D] = self.boxes2d[D]
         self.seg_cnt = torch.zeros((D, S), **i32)
-        self.slot_box, self.n_kept = torch.full((B1,), D, **i32), torch.zeros((1,), **i32)
         self.slot_frame, self.slot_class = torch.zeros((B1,), **i32), torch.zeros((B1,), **i32)
         self.slot_group = torch.full((B1,), spare_group, **i32)
-        self.seg_off, self.off, self.counts = torch.zeros((D * S + 1,), **i64), torch.zeros((B1 + 1,), **i64), torch.zeros((B1,), **i64)
-        # the spare row is what an empty slot's all-zero choice row reads: fcn_prepare_inputs_infer indexes off[b] + choice
-        self.points = torch.zeros((capacity + 1, ps), **f32)
         self.t = {"raw": self.points, "off": self.off, "choice": torch.zeros((B1, N), **i32), "fangle": torch.zeros((B1,), **f64),
                   "box2d": torch.zeros((B1, 4), **f64), "P": torch.zeros((B1, 12), **f64), "B": B1, "pt_stride": ps}
         self.scalars = (torch.zeros((B1,), **f64), torch.zeros((B1,), **f64))          # the draw's coin and normal: unused
@@ -913,9 +789,7 @@ class FrameDetectSource:
     @staticmethod
     def limits():
         """(the largest D, the largest D * S) of the plan."""
-        a, b = ctypes.c_int(0), ctypes.c_int(0)
-        _native.check(_native.lib().fcn_frustum_detect_plan_limits(ctypes.byref(a), ctypes.byref(b)), "fcn_frustum_detect_plan_limits")
-        return a.value, b.value
+        return resident.limits("fcn_frustum_detect_plan_limits", 2)
 
     def bind(self, fov_off=None, slot_frame=None, slot_class=None, slot_group=None):
         """Points outputs of step() at tensors of the caller (cascade.FrameCascade: the link's frame offsets and frustum tables):
@@ -935,31 +809,7 @@ class FrameDetectSource:
         """Fills rows 0..n-1 of the detection table and n_boxes in place from host sequences of n <= D boxes (validated here: finite
         boxes, frames in [0, F), class names of builder.classes, finite scores, groups in [0, spare_group); unit_group None: every
         box its own group, which needs n <= spare_group).  An upload: not for a captured region."""
-        who = "FrameDetectSource.set_boxes"
-        host = lambda a: (a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a))
-        boxes = np.ascontiguousarray(host(boxes2d), dtype=np.float64).reshape(-1, 4)
-        fr, pr = np.ascontiguousarray(host(box_frame)).reshape(-1), np.ascontiguousarray(host(prob), dtype=np.float32).reshape(-1)
-        n = len(boxes)
-        ug = np.arange(n) if unit_group is None else np.ascontiguousarray(host(unit_group)).reshape(-1)
-        types = [str(t) for t in types]
-        if n > self.D or len(fr) != n or len(pr) != n or len(ug) != n or len(types) != n:
-            raise ValueError("%s: %d boxes (at most %d), %d frames, %d types, %d scores, %d groups" %
-                             (who, n, self.D, len(fr), len(types), len(pr), len(ug)))
-        if n and (fr.dtype.kind not in "iu" or ug.dtype.kind not in "iu" or fr.min() < 0 or fr.max() >= self.F or ug.min() < 0 or
-                  ug.max() >= self.spare_group):
-            raise ValueError("%s: frames must be integers in [0, %d) and groups integers in [0, %d)" % (who, self.F, self.spare_group))
-        if not (np.isfinite(boxes).all() and np.isfinite(pr).all()):
-            raise ValueError("%s: boxes and scores must be finite" % who)
-        cls = [self.builder.classes.index(t) if t in self.builder.classes else -1 for t in types]
-        if n and min(cls) < 0:
-            raise ValueError("%s: type %r is not one of %r" % (who, types[cls.index(-1)], tuple(self.builder.classes)))
-        up = lambda a, dt: torch.from_numpy(np.ascontiguousarray(np.asarray(a, dtype=dt)))
-        if n:
-            self.boxes2d[:n].copy_(up(boxes, np.float64))
-            self.box_prob[:n].copy_(up(pr, np.float32))
-            for dst, src in ((self.box_frame, fr), (self.box_class, cls), (self.box_group, ug)):
-                dst[:n].copy_(up(src, np.int32))
-        self.n_boxes.fill_(n)
+        self.table.set_boxes("FrameDetectSource.set_boxes", boxes2d, box_frame, types, prob, unit_group)
         return self
 
     def step(self):
@@ -999,10 +849,8 @@ class FrameDetectSource:
                 _native.check(L.fcn_frustum_fov_plan(p(self.fov_cnt), F, S, int(pts.shape[0]), p(self.fov_seg_off), p(self.fov_off), s),
                               "fcn_frustum_fov_plan")
                 _native.check(L.fcn_frustum_detect_fill(*fargs, p(self.fov_seg_off), p(self.fov_points), s), "fcn_frustum_detect_fill")
-        res = dict(out)
-        res.update(slot_box=self.slot_box, slot_frame=self.slot_frame, slot_class=self.slot_class, slot_group=self.slot_group,
-                   n_kept=self.n_kept)
-        return res
+        return dict(out, slot_box=self.slot_box, slot_frame=self.slot_frame, slot_class=self.slot_class, slot_group=self.slot_group,
+                    n_kept=self.n_kept)
 
     def check(self):
         """Reads the status words of the plan and the draws (a synchronisation: not for a captured region); raises ValueError naming
@@ -1040,32 +888,20 @@ class SunrgbdDetectSource:
 
     def __init__(self, frame_points, frame_off, K, Rtilt, builder, B, D, capacity, seed, cap=SUNRGBD_CAP, point_threshold=SUNRGBD_MIN,
                  sub=None, choice=None):
-        from .inputs import DeviceDraws
         who = "SunrgbdDetectSource"
-        if not (isinstance(frame_points, torch.Tensor) and frame_points.is_cuda and frame_points.dtype == torch.float32 and
-                frame_points.is_contiguous() and frame_points.dim() == 2 and frame_points.shape[0] >= 1 and not frame_points.requires_grad):
-            raise ValueError("%s: frame_points must be a contiguous (n >= 1, >= 3) float32 device tensor (it is held, not copied)" % who)
+        resident.held(who, frame_points)
         pts, foff, F, ps, S = _frames(who, frame_points, frame_off, resident=True)
         dev = frame_points.device
-        cal = []
-        for name, m in (("K", K), ("Rtilt", Rtilt)):
-            t = torch.as_tensor(m).to(device=dev, dtype=torch.float64).contiguous()
-            if t.numel() != F * 9:
-                raise ValueError("%s: %s must hold %d x 9 numbers, got %s" % (who, name, F, tuple(t.shape)))
-            cal.append(t.view(F, 9))
-        if builder.device.type != "cuda":
-            raise RuntimeError("frustum_convnet_amd: input construction is a HIP kernel (MI355X only); no CPU fallback")
+        cal = resident.intrinsics(who, K, Rtilt, F, dev)
+        resident.need_device_builder(builder)
         B, D, capacity, cap, point_threshold = int(B), int(D), int(capacity), int(cap), int(point_threshold)
         max_d, max_segs, max_cap = self.limits()
         N, C = builder.npoints, len(builder.classes)
-        if not (1 <= B <= D <= max_d):
-            raise ValueError("%s: need 1 <= B <= D <= %d, got B = %d, D = %d" % (who, max_d, B, D))
-        if D * S > max_segs:
-            raise ValueError("%s: D * S = %d * %d segments exceed the plan's %d" % (who, D, S, max_segs))
+        resident.check_slots(who, B, D, max_d)
+        resident.check_segments(who, D, S, max_segs)
         if not (1 <= cap <= max_cap) or not (1 <= N <= max_cap):
             raise ValueError("%s: cap and the builder's npoints must lie in [1, %d], got %d, %d" % (who, max_cap, cap, N))
-        if capacity < 1:
-            raise ValueError("%s: capacity must be >= 1 row, got %d" % (who, capacity))
+        resident.check_capacity(who, capacity)
         if F * C >= 2 ** 31 or abs(point_threshold) >= 2 ** 31:
             raise ValueError("%s: F * C = %d groups and point_threshold = %d must fit int32" % (who, F * C, point_threshold))
         for name, t, n in (("sub", sub, B * cap), ("choice", choice, B * N)):
@@ -1078,25 +914,21 @@ class SunrgbdDetectSource:
         f32, f64, i32, i64 = (dict(dtype=t, device=dev) for t in (torch.float32, torch.float64, torch.int32, torch.int64))
         # ---- resident: the frames (held), the calibration, the detection table with its spare row D
         self.frames = (pts, foff, cal[0], cal[1])
-        self.boxes2d = torch.zeros((D + 1, 4), **f64)
-        self.boxes2d[D] = torch.tensor([0.0, 0.0, 1.0, 1.0], **f64)
-        self.box_frame, self.box_class = torch.zeros((D + 1,), **i32), torch.zeros((D + 1,), **i32)
-        self.box_prob, self.n_boxes = torch.zeros((D + 1,), **f32), torch.zeros((1,), **i32)
+        self.table = DetectTable(dev, D, F, builder.classes)
+        resident.adopt(self, self.table)
         self.eye = torch.eye(C, **f32)
         self.draws, self.draws_sub = DeviceDraws(int(seed), builder.device), DeviceDraws(int(seed) + 1, builder.device)
-        self.status = torch.zeros((1,), **i32)
-        # ---- every intermediate.  angle has D + 1 entries as well: entry D is what an empty slot gathers, zero, never written by a kernel
+        # ---- the batch and every intermediate.  angle has D + 1 entries as well: entry D is what an empty slot gathers, zero, never
+        # written by a kernel
+        self.points, self.seg_off, self.off, self.counts, self.slot_box, self.n_kept, self.status = \
+            resident.batch_skeleton(dev, B, D, S, capacity, ps, D)
         self.angle, self.seg_cnt = torch.zeros((D + 1,), **f64), torch.zeros((D, S), **i32)
-        self.slot_box, self.n_kept = torch.full((B,), D, **i32), torch.zeros((1,), **i32)
         self.slot_frame, self.slot_class = torch.zeros((B,), **i32), torch.zeros((B,), **i32)
         self.slot_group = torch.full((B,), F * C, **i32)
-        self.seg_off, self.off, self.counts = torch.zeros((D * S + 1,), **i64), torch.zeros((B + 1,), **i64), torch.zeros((B,), **i64)
         self.cnt32, self.sub_off = torch.zeros((B,), **i32), torch.zeros((B + 1,), **i64)
         self.sub_start, self.sub_len = torch.zeros((B,), **i64), torch.zeros((B,), **i32)
         self.fixed_sub, self.fixed_choice = sub is not None, choice
         self.sub = sub.view(-1) if self.fixed_sub else torch.zeros((B * cap,), **i32)
-        # the spare row is what an empty slot's all-zero choice row reads: fcn_prepare_inputs_sunrgbd_infer indexes off[b] + choice
-        self.points = torch.zeros((capacity + 1, ps), **f32)
         self.t = {"raw": self.points, "off": self.off, "choice": torch.zeros((B, N), **i32), "fangle": torch.zeros((B,), **f64),
                   "box2d": torch.zeros((B, 4), **f64), "K": torch.zeros((B, 9), **f64), "R": torch.zeros((B, 9), **f64), "B": B,
                   "pt_stride": ps}
@@ -1106,37 +938,12 @@ class SunrgbdDetectSource:
     @staticmethod
     def limits():
         """(the largest D, the largest D * S, the largest cap and npoints) of the kernels."""
-        a, b, c, d = (ctypes.c_int(0) for _ in range(4))
-        L = _native.lib()
-        _native.check(L.fcn_frustum_detect_plan_limits(ctypes.byref(a), ctypes.byref(b)), "fcn_frustum_detect_plan_limits")
-        _native.check(L.fcn_draw_limits(ctypes.byref(c), ctypes.byref(d)), "fcn_draw_limits")
-        return a.value, b.value, c.value
+        return resident.limits("fcn_frustum_detect_plan_limits", 2) + resident.limits("fcn_draw_limits", 2)[:1]
 
     def set_boxes(self, boxes2d, box_frame, types, prob):
         """Fills rows 0..n-1 of the detection table and n_boxes in place from host sequences of n <= D boxes (validated here: finite
         boxes, frames in [0, F), class names of builder.classes, finite scores).  An upload: not for a captured region."""
-        who = "SunrgbdDetectSource.set_boxes"
-        host = lambda a: (a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a))
-        boxes = np.ascontiguousarray(host(boxes2d), dtype=np.float64).reshape(-1, 4)
-        fr, pr = np.ascontiguousarray(host(box_frame)).reshape(-1), np.ascontiguousarray(host(prob), dtype=np.float32).reshape(-1)
-        n = len(boxes)
-        types = [str(t) for t in types]
-        if n > self.D or len(fr) != n or len(pr) != n or len(types) != n:
-            raise ValueError("%s: %d boxes (at most %d), %d frames, %d types, %d scores" % (who, n, self.D, len(fr), len(types), len(pr)))
-        if n and (fr.dtype.kind not in "iu" or fr.min() < 0 or fr.max() >= self.F):
-            raise ValueError("%s: frames must be integers in [0, %d)" % (who, self.F))
-        if not (np.isfinite(boxes).all() and np.isfinite(pr).all()):
-            raise ValueError("%s: boxes and scores must be finite" % who)
-        cls = [self.builder.classes.index(t) if t in self.builder.classes else -1 for t in types]
-        if n and min(cls) < 0:
-            raise ValueError("%s: type %r is not one of %r" % (who, types[cls.index(-1)], tuple(self.builder.classes)))
-        up = lambda a, dt: torch.from_numpy(np.ascontiguousarray(np.asarray(a, dtype=dt)))
-        if n:
-            self.boxes2d[:n].copy_(up(boxes, np.float64))
-            self.box_prob[:n].copy_(up(pr, np.float32))
-            for dst, src in ((self.box_frame, fr), (self.box_class, cls)):
-                dst[:n].copy_(up(src, np.int32))
-        self.n_boxes.fill_(n)
+        self.table.set_boxes("SunrgbdDetectSource.set_boxes", boxes2d, box_frame, types, prob)
         return self
 
     def step(self):
@@ -1178,10 +985,8 @@ class SunrgbdDetectSource:
             if self.fixed_sub or self.fixed_choice is not None:
                 self._compose()
             bld.launch_infer(t, out)
-        res = dict(out)
-        res.update(slot_box=self.slot_box, slot_frame=self.slot_frame, slot_class=self.slot_class, slot_group=self.slot_group,
-                   n_kept=self.n_kept)
-        return res
+        return dict(out, slot_box=self.slot_box, slot_frame=self.slot_frame, slot_class=self.slot_class, slot_group=self.slot_group,
+                    n_kept=self.n_kept)
 
     def _compose(self):
         """The override tables into t["choice"]: a given choice indexes the slot's record, so it goes through the slot's subsample
