@@ -43,6 +43,67 @@ __device__ __forceinline__ bool inp_in_box(double dx, double dy, double dz, doub
     return fabs(lx) <= l / 2.0 && fabs(dy) <= h / 2.0 && fabs(lz) <= w / 2.0;
 }
 
+// ---- what the two kernels below share.  The first stage passes the origin 0 and the scales 0.5 / 1.0 where its text used to
+// have no operation at all: x - 0.0 and x * 1.0 are x for every IEEE double (either zero keeps its sign, an infinity and a NaN
+// stay what they are), so the bits are the ones of the unshared statements.
+struct InpBox { double cx, cy, cz, ang, sl, sw, sh; };   // the label box in the sample's frame: centre, heading, size (l, w, h)
+
+// A: InpArgs or InpRefineArgs -- the members the helpers read have the same names in both, and each is read where it is used.
+// Label box of sample b: its centre (the mean of corners 0 and 6) relative to the origin o, rotated by rot (c, s = cos, sin);
+// heading minus rot; the x-flip; the size as it came.
+template <class A> __device__ __forceinline__ void inp_label_box(InpBox &k, const A &a, int b, double ox, double oy, double oz,
+                                                                 double rot, double c, double s, bool flip)
+{
+    const double *cr = a.corners + (int64_t)b * 24;
+    const double dx = (cr[0] + cr[18]) / 2.0 - ox, dy = (cr[1] + cr[19]) / 2.0 - oy, dz = (cr[2] + cr[20]) / 2.0 - oz;
+    k.cx = dx * c + dz * (-s); k.cy = dy; k.cz = dx * s + dz * c;
+    k.ang = a.heading[b] - rot;
+    if (flip) { k.cx = -k.cx; k.ang = M_PI - k.ang; }
+    k.sl = a.size[3 * b]; k.sw = a.size[3 * b + 1]; k.sh = a.size[3 * b + 2];
+}
+
+template <class A> __device__ __forceinline__ void inp_store_box(const InpBox &k, const A &a, int b)
+{
+    a.center[3 * b] = (float)k.cx; a.center[3 * b + 1] = (float)k.cy; a.center[3 * b + 2] = (float)k.cz;
+    a.head[b] = (float)k.ang;
+    a.osize[3 * b] = (float)k.sl; a.osize[3 * b + 1] = (float)k.sw; a.osize[3 * b + 2] = (float)k.sh;
+}
+
+// Window centre l of sample b's row of L labels, at (x, y, z): +1 inside the box scaled by f1, -1 inside the one scaled by f2, else 0; the thread's nearest centre
+// so far (l ascends per thread: the first minimum is kept) and whether it has seen a positive.
+template <class A> __device__ __forceinline__ void inp_classify(const A &a, int b, int L, int l, double x, double y, double z,
+                                                                const InpBox &k, double ca, double sa, double f1, double f2,
+                                                                bool &any1, double &best, int &bidx)
+{
+    const double dx = x - k.cx, dy = y - k.cy, dz = z - k.cz;
+    const bool in1 = inp_in_box(dx, dy, dz, ca, sa, k.sl * f1, k.sw * f1, k.sh * f1);
+    const bool in2 = inp_in_box(dx, dy, dz, ca, sa, k.sl * f2, k.sw * f2, k.sh * f2);
+    a.cls[(int64_t)b * L + l] = in1 ? 1 : (in2 ? -1 : 0);
+    any1 = any1 || in1;
+    const double dd = sqrt(dx * dx + dy * dy + dz * dz);
+    if (dd < best) { best = dd; bidx = l; }
+}
+
+// After the window loop, by every thread of the workgroup: when nobody saw a centre inside the inner box, the nearest centre is
+// the positive (np.argmin: the first of equal minima).  *sany is zeroed, behind a barrier, before the loop.
+template <class A> __device__ __forceinline__ void inp_nearest_positive(const A &a, int b, int L, double *sdist, int *sidx, int *sany,
+                                                                        int tid, bool any1, double best, int bidx)
+{
+    if (any1) *sany = 1;
+    sdist[tid] = best; sidx[tid] = bidx;
+    __syncthreads();
+    if (*sany) return;
+    for (int o = INP_T / 2; o > 0; o >>= 1) {
+        if (tid < o) {
+            const double d2 = sdist[tid + o];
+            const int i2 = sidx[tid + o];
+            if (d2 < sdist[tid] || (d2 == sdist[tid] && i2 < sidx[tid])) { sdist[tid] = d2; sidx[tid] = i2; }
+        }
+        __syncthreads();
+    }
+    if (tid == 0 && sidx[0] != 0x7fffffff) a.cls[(int64_t)b * L + sidx[0]] = 1;
+}
+
 __global__ __launch_bounds__(INP_T) void prepare_inputs_kernel(InpArgs a)
 {
     __shared__ double sdist[INP_T];
@@ -55,34 +116,23 @@ __global__ __launch_bounds__(INP_T) void prepare_inputs_kernel(InpArgs a)
     const double c = cos(rot), s = sin(rot);
     // corners == nullptr: inference records (fcn_prepare_inputs_infer) -- no label box, so no flip, no shift and no label outputs
     const bool train = a.corners != nullptr;
-    double cx = 0.0, cy = 0.0, cz = 0.0, ang = 0.0, sl = 0.0, sw = 0.0, sh = 0.0;
+    InpBox k = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     const bool flip = train && a.d.random_flip && a.coin[b] > 0.5;
-    if (train) {
-        const double *cr = a.corners + (int64_t)b * 24;
-        const double c0x = (cr[0] + cr[18]) / 2.0, c0y = (cr[1] + cr[19]) / 2.0, c0z = (cr[2] + cr[20]) / 2.0;
-        cx = c0x * c + c0z * (-s); cy = c0y; cz = c0x * s + c0z * c;        // (cy: the height shift below moves it)
-        ang = a.heading[b] - rot;
-        if (flip) { cx = -cx; ang = M_PI - ang; }
-        sl = a.size[3 * b]; sw = a.size[3 * b + 1]; sh = a.size[3 * b + 2];
-    }
+    if (train) inp_label_box(k, a, b, 0.0, 0.0, 0.0, rot, c, s, flip);
     const bool do_shift = train && a.d.random_shift;
     double shift = 0.0;
     if (do_shift) {
-        const double dist = sqrt(sl * sl + sw * sw);
+        const double dist = sqrt(k.sl * k.sl + k.sw * k.sw);
         shift = fmin(fmax(a.normal[b] * dist * 0.2, -0.5 * dist), 0.5 * dist);
-        shift = fmin(fmax(shift + cz, 0.0), a.d.max_depth) - cz;
-        cz += shift;
+        shift = fmin(fmax(shift + k.cz, 0.0), a.d.max_depth) - k.cz;
+        k.cz += shift;
     }
     // provider_sample_sunrgbd.py:228-230: height_shift = np.random.random() * 0.4 - 0.2 on the points' y and the box centre
     const bool has_h = do_shift && a.hshift != nullptr;
     const double hsh = has_h ? a.hshift[b] * 0.4 - 0.2 : 0.0;
-    if (has_h) cy += hsh;
+    if (has_h) k.cy += hsh;
     if (tid == 0) {
-        if (train) {
-            a.center[3 * b] = (float)cx; a.center[3 * b + 1] = (float)cy; a.center[3 * b + 2] = (float)cz;
-            a.head[b] = (float)ang;
-            a.osize[3 * b] = (float)sl; a.osize[3 * b + 1] = (float)sw; a.osize[3 * b + 2] = (float)sh;
-        }
+        if (train) inp_store_box(k, a, b);
         a.rot[b] = (float)rot;
     }
     // ---- points
@@ -116,7 +166,7 @@ __global__ __launch_bounds__(INP_T) void prepare_inputs_kernel(InpArgs a)
         for (int i = 0; i < 9; ++i) Rt[i] = a.Rtilt[(int64_t)b * 9 + i];
     }
     const double u0 = (a.box2d[4 * b] + a.box2d[4 * b + 2]) / 2.0, v0 = (a.box2d[4 * b + 1] + a.box2d[4 * b + 3]) / 2.0;
-    const double ca = cos(ang), sa = sin(ang);
+    const double ca = cos(k.ang), sa = sin(k.ang);
     double best = 1e300;
     int bidx = 0x7fffffff;
     bool any1 = false;
@@ -143,32 +193,55 @@ __global__ __launch_bounds__(INP_T) void prepare_inputs_kernel(InpArgs a)
             if (flip) xr = -xr;
             float *o = a.ref[sc] + (int64_t)b * 3 * L;
             o[l] = (float)xr; o[L + l] = (float)y; o[2 * L + l] = (float)zr;
-            if (sc == 1 && a.cls) {
-                const double dx = xr - cx, dy = y - cy, dz = zr - cz;
-                const bool in1 = inp_in_box(dx, dy, dz, ca, sa, sl * 0.5, sw * 0.5, sh * 0.5);
-                const bool in2 = inp_in_box(dx, dy, dz, ca, sa, sl, sw, sh);
-                a.cls[(int64_t)b * L + l] = in1 ? 1 : (in2 ? -1 : 0);
-                any1 = any1 || in1;
-                const double dd = sqrt(dx * dx + dy * dy + dz * dz);
-                if (dd < best) { best = dd; bidx = l; }       // l ascends per thread: first minimum kept
-            }
+            if (sc == 1 && a.cls)                              // the half-size box is the positive, the full box the ignore region
+                inp_classify(a, b, L, l, xr, y, zr, k, ca, sa, 0.5, 1.0, any1, best, bidx);
         }
     }
     if (!a.cls) return;
-    if (any1) sany = 1;
-    sdist[tid] = best; sidx[tid] = bidx;
-    __syncthreads();
-    if (sany) return;
-    // nobody inside the half-size box: the nearest centre is the positive (np.argmin: first of equal minima)
-    for (int o = INP_T / 2; o > 0; o >>= 1) {
-        if (tid < o) {
-            const double d2 = sdist[tid + o];
-            const int i2 = sidx[tid + o];
-            if (d2 < sdist[tid] || (d2 == sdist[tid] && i2 < sidx[tid])) { sdist[tid] = d2; sidx[tid] = i2; }
-        }
-        __syncthreads();
-    }
-    if (tid == 0 && sidx[0] != 0x7fffffff) a.cls[(int64_t)b * a.d.L[1] + sidx[0]] = 1;
+    inp_nearest_positive(a, b, a.d.L[1], sdist, sidx, &sany, tid, any1, best, bidx);
+}
+
+// Every scale of a descriptor has windows, a positive stride (a NaN is refused) and an output.
+static bool inp_scales_ok(int nsc, const int32_t *L, const double *stride, float *const *center_ref)
+{
+    for (int s = 0; s < nsc; ++s)
+        if (L[s] <= 0 || !(stride[s] > 0.0) || !center_ref[s]) return false;
+    return true;
+}
+
+template <class D> static InpDescG inp_view(const D *d, int nsc)      // fcn_inp_desc / fcn_inp5_desc in the kernel's one shape
+{
+    InpDescG v = {d->B, d->N, d->pt_stride, nsc, {0, 0, 0, 0, 0}, {1.0, 1.0, 1.0, 1.0, 1.0}, d->max_depth, d->random_flip, d->random_shift};
+    for (int s = 0; s < nsc; ++s) { v.L[s] = d->L[s]; v.stride[s] = d->stride[s]; }
+    return v;
+}
+
+// The checks and the launch of the four first-stage entries below.  The calibration is P, or K and Rtilt with P == nullptr.
+// labels: the entry takes a label box -- corners, heading, size and the three box outputs are required then, coin / normal where the
+// descriptor asks for flip / shift, raw_seg beside seg_label; cls_label and seg_label stay optional.  Without, the entry passes
+// nullptr for all of them.
+static int inp_first_stage(const InpDescG &v, bool labels, const float *raw_pts, const int64_t *pt_off, const int64_t *raw_seg,
+                           const int32_t *choice, const double *frustum_angle, const double *box2d, const double *P, const double *K,
+                           const double *Rtilt, const double *box3d_corners, const double *heading, const double *size,
+                           const double *coin, const double *normal, const double *hshift, float *point_cloud,
+                           float *const *center_ref, int64_t *cls_label, float *box3d_center, float *box3d_heading,
+                           float *box3d_size, float *rot_angle, int64_t *seg_label, void *stream)
+{
+    if (!raw_pts || !pt_off || !choice || !frustum_angle || !box2d || !(P || (K && Rtilt)) || !point_cloud || !center_ref || !rot_angle)
+        return FCN_E_BADARG;
+    if (labels && (!box3d_corners || !heading || !size || !box3d_center || !box3d_heading || !box3d_size)) return FCN_E_BADARG;
+    if (v.B <= 0 || v.N <= 0 || v.pt_stride < 3) return FCN_E_BADARG;
+    if ((v.random_flip && !coin) || (v.random_shift && !normal) || (seg_label && !raw_seg)) return FCN_E_BADARG;
+    if (!inp_scales_ok(v.nsc, v.L, v.stride, center_ref)) return FCN_E_BADARG;
+    InpArgs a;
+    a.d = v; a.raw = raw_pts; a.off = pt_off; a.raw_seg = raw_seg; a.choice = choice; a.fangle = frustum_angle; a.box2d = box2d;
+    a.P = P; a.K = K; a.Rtilt = Rtilt; a.corners = box3d_corners; a.heading = heading; a.size = size; a.coin = coin;
+    a.normal = normal; a.hshift = hshift; a.pc = point_cloud; a.cls = cls_label; a.center = box3d_center; a.head = box3d_heading;
+    a.osize = box3d_size; a.rot = rot_angle; a.seg = seg_label;
+    for (int s = 0; s < 5; ++s) a.ref[s] = s < v.nsc ? center_ref[s] : nullptr;
+    hipLaunchKernelGGL(prepare_inputs_kernel, dim3(v.B), dim3(INP_T), 0, (hipStream_t)stream, a);
+    FCN_CHECK_LAUNCH();
+    return 0;
 }
 
 extern "C" int fcn_prepare_inputs(const fcn_inp_desc *d, const float *raw_pts, const int64_t *pt_off, const int64_t *raw_seg,
@@ -178,26 +251,10 @@ extern "C" int fcn_prepare_inputs(const fcn_inp_desc *d, const float *raw_pts, c
                                   int64_t *cls_label, float *box3d_center, float *box3d_heading, float *box3d_size,
                                   float *rot_angle, int64_t *seg_label, void *stream)
 {
-    if (!d || !raw_pts || !pt_off || !choice || !frustum_angle || !box2d || !P || !point_cloud || !center_ref ||
-        !box3d_center || !box3d_heading || !box3d_size || !rot_angle)
-        return FCN_E_BADARG;
-    if (!box3d_corners || !heading || !size) return FCN_E_BADARG;
-    if (d->B <= 0 || d->N <= 0 || d->pt_stride < 3) return FCN_E_BADARG;
-    if ((d->random_flip && !coin) || (d->random_shift && !normal) || (seg_label && !raw_seg)) return FCN_E_BADARG;
-    for (int s = 0; s < 4; ++s)
-        if (d->L[s] <= 0 || !(d->stride[s] > 0.0) || !center_ref[s]) return FCN_E_BADARG;
-    InpArgs a;
-    a.d.B = d->B; a.d.N = d->N; a.d.pt_stride = d->pt_stride; a.d.nsc = 4; a.d.max_depth = d->max_depth;
-    a.d.random_flip = d->random_flip; a.d.random_shift = d->random_shift;
-    for (int s = 0; s < 5; ++s) { a.d.L[s] = s < 4 ? d->L[s] : 0; a.d.stride[s] = s < 4 ? d->stride[s] : 1.0; a.ref[s] = s < 4 ? center_ref[s] : nullptr; }
-    a.raw = raw_pts; a.off = pt_off; a.raw_seg = raw_seg; a.choice = choice; a.fangle = frustum_angle;
-    a.box2d = box2d; a.P = P; a.corners = box3d_corners; a.heading = heading; a.size = size; a.coin = coin; a.normal = normal;
-    a.K = nullptr; a.Rtilt = nullptr; a.hshift = nullptr;
-    a.pc = point_cloud;
-    a.cls = cls_label; a.center = box3d_center; a.head = box3d_heading; a.osize = box3d_size; a.rot = rot_angle; a.seg = seg_label;
-    hipLaunchKernelGGL(prepare_inputs_kernel, dim3(d->B), dim3(INP_T), 0, (hipStream_t)stream, a);
-    FCN_CHECK_LAUNCH();
-    return 0;
+    if (!d) return FCN_E_BADARG;
+    return inp_first_stage(inp_view(d, 4), true, raw_pts, pt_off, raw_seg, choice, frustum_angle, box2d, P, nullptr, nullptr,
+                           box3d_corners, heading, size, coin, normal, nullptr, point_cloud, center_ref, cls_label, box3d_center,
+                           box3d_heading, box3d_size, rot_angle, seg_label, stream);
 }
 
 // Inference records of the first stage (datasets/provider_sample.py:184-195, from_rgb_detection): no label box in, no labels out,
@@ -206,27 +263,14 @@ extern "C" int fcn_prepare_inputs_infer(const fcn_inp_desc *d, const float *raw_
                                         const double *frustum_angle, const double *box2d, const double *P, float *point_cloud,
                                         float *const center_ref[4], float *rot_angle, void *stream)
 {
-    if (!d || !raw_pts || !pt_off || !choice || !frustum_angle || !box2d || !P || !point_cloud || !center_ref || !rot_angle)
-        return FCN_E_BADARG;
-    if (d->B <= 0 || d->N <= 0 || d->pt_stride < 3 || d->random_flip || d->random_shift) return FCN_E_BADARG;
-    for (int s = 0; s < 4; ++s)
-        if (d->L[s] <= 0 || !(d->stride[s] > 0.0) || !center_ref[s]) return FCN_E_BADARG;
-    InpArgs a;
-    a.d.B = d->B; a.d.N = d->N; a.d.pt_stride = d->pt_stride; a.d.nsc = 4; a.d.max_depth = d->max_depth;
-    a.d.random_flip = 0; a.d.random_shift = 0;
-    for (int s = 0; s < 5; ++s) { a.d.L[s] = s < 4 ? d->L[s] : 0; a.d.stride[s] = s < 4 ? d->stride[s] : 1.0; a.ref[s] = s < 4 ? center_ref[s] : nullptr; }
-    a.raw = raw_pts; a.off = pt_off; a.raw_seg = nullptr; a.choice = choice; a.fangle = frustum_angle;
-    a.box2d = box2d; a.P = P; a.corners = nullptr; a.heading = nullptr; a.size = nullptr; a.coin = nullptr; a.normal = nullptr;
-    a.K = nullptr; a.Rtilt = nullptr; a.hshift = nullptr;
-    a.pc = point_cloud;
-    a.cls = nullptr; a.center = nullptr; a.head = nullptr; a.osize = nullptr; a.rot = rot_angle; a.seg = nullptr;
-    hipLaunchKernelGGL(prepare_inputs_kernel, dim3(d->B), dim3(INP_T), 0, (hipStream_t)stream, a);
-    FCN_CHECK_LAUNCH();
-    return 0;
+    if (!d || d->random_flip || d->random_shift) return FCN_E_BADARG;
+    return inp_first_stage(inp_view(d, 4), false, raw_pts, pt_off, nullptr, choice, frustum_angle, box2d, P, nullptr, nullptr,
+                           nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, point_cloud, center_ref, nullptr, nullptr, nullptr,
+                           nullptr, rot_angle, nullptr, stream);
 }
 
 // SUN-RGBD loader (cfgs/det_sample_sunrgbd.yaml; datasets/provider_sample_sunrgbd.py:116-326): five strides, centres through
-// K and Rtilt, depth + height shift.
+// K and Rtilt, depth + height shift (the kernel applies the latter where it is handed hshift).
 extern "C" int fcn_prepare_inputs_sunrgbd(const fcn_inp5_desc *d, const float *raw_pts, const int64_t *pt_off,
                                           const int64_t *raw_seg, const int32_t *choice, const double *frustum_angle,
                                           const double *box2d, const double *K, const double *Rtilt,
@@ -236,26 +280,10 @@ extern "C" int fcn_prepare_inputs_sunrgbd(const fcn_inp5_desc *d, const float *r
                                           float *box3d_center, float *box3d_heading, float *box3d_size, float *rot_angle,
                                           int64_t *seg_label, void *stream)
 {
-    if (!d || !raw_pts || !pt_off || !choice || !frustum_angle || !box2d || !K || !Rtilt || !point_cloud || !center_ref ||
-        !box3d_center || !box3d_heading || !box3d_size || !rot_angle)
-        return FCN_E_BADARG;
-    if (!box3d_corners || !heading || !size) return FCN_E_BADARG;
-    if (d->B <= 0 || d->N <= 0 || d->pt_stride < 3) return FCN_E_BADARG;
-    if ((d->random_flip && !coin) || (d->random_shift && (!normal || !hshift)) || (seg_label && !raw_seg)) return FCN_E_BADARG;
-    for (int s = 0; s < 5; ++s)
-        if (d->L[s] <= 0 || !(d->stride[s] > 0.0) || !center_ref[s]) return FCN_E_BADARG;
-    InpArgs a;
-    a.d.B = d->B; a.d.N = d->N; a.d.pt_stride = d->pt_stride; a.d.nsc = 5; a.d.max_depth = d->max_depth;
-    a.d.random_flip = d->random_flip; a.d.random_shift = d->random_shift;
-    for (int s = 0; s < 5; ++s) { a.d.L[s] = d->L[s]; a.d.stride[s] = d->stride[s]; a.ref[s] = center_ref[s]; }
-    a.raw = raw_pts; a.off = pt_off; a.raw_seg = raw_seg; a.choice = choice; a.fangle = frustum_angle;
-    a.box2d = box2d; a.P = nullptr; a.corners = box3d_corners; a.heading = heading; a.size = size; a.coin = coin; a.normal = normal;
-    a.K = K; a.Rtilt = Rtilt; a.hshift = d->random_shift ? hshift : nullptr;
-    a.pc = point_cloud;
-    a.cls = cls_label; a.center = box3d_center; a.head = box3d_heading; a.osize = box3d_size; a.rot = rot_angle; a.seg = seg_label;
-    hipLaunchKernelGGL(prepare_inputs_kernel, dim3(d->B), dim3(INP_T), 0, (hipStream_t)stream, a);
-    FCN_CHECK_LAUNCH();
-    return 0;
+    if (!d || (d->random_shift && !hshift)) return FCN_E_BADARG;
+    return inp_first_stage(inp_view(d, 5), true, raw_pts, pt_off, raw_seg, choice, frustum_angle, box2d, nullptr, K, Rtilt,
+                           box3d_corners, heading, size, coin, normal, d->random_shift ? hshift : nullptr, point_cloud, center_ref,
+                           cls_label, box3d_center, box3d_heading, box3d_size, rot_angle, seg_label, stream);
 }
 
 // Inference records of the SUN-RGBD loader (provider_sample_sunrgbd.py:165-186, from_rgb_detection): the same kernel with
@@ -265,23 +293,10 @@ extern "C" int fcn_prepare_inputs_sunrgbd_infer(const fcn_inp5_desc *d, const fl
                                                 const double *K, const double *Rtilt, float *point_cloud,
                                                 float *const center_ref[5], float *rot_angle, void *stream)
 {
-    if (!d || !raw_pts || !pt_off || !choice || !frustum_angle || !box2d || !K || !Rtilt || !point_cloud || !center_ref || !rot_angle)
-        return FCN_E_BADARG;
-    if (d->B <= 0 || d->N <= 0 || d->pt_stride < 3 || d->random_flip || d->random_shift) return FCN_E_BADARG;
-    for (int s = 0; s < 5; ++s)
-        if (d->L[s] <= 0 || !(d->stride[s] > 0.0) || !center_ref[s]) return FCN_E_BADARG;
-    InpArgs a;
-    a.d.B = d->B; a.d.N = d->N; a.d.pt_stride = d->pt_stride; a.d.nsc = 5; a.d.max_depth = d->max_depth;
-    a.d.random_flip = 0; a.d.random_shift = 0;
-    for (int s = 0; s < 5; ++s) { a.d.L[s] = d->L[s]; a.d.stride[s] = d->stride[s]; a.ref[s] = center_ref[s]; }
-    a.raw = raw_pts; a.off = pt_off; a.raw_seg = nullptr; a.choice = choice; a.fangle = frustum_angle;
-    a.box2d = box2d; a.P = nullptr; a.corners = nullptr; a.heading = nullptr; a.size = nullptr; a.coin = nullptr; a.normal = nullptr;
-    a.K = K; a.Rtilt = Rtilt; a.hshift = nullptr;
-    a.pc = point_cloud;
-    a.cls = nullptr; a.center = nullptr; a.head = nullptr; a.osize = nullptr; a.rot = rot_angle; a.seg = nullptr;
-    hipLaunchKernelGGL(prepare_inputs_kernel, dim3(d->B), dim3(INP_T), 0, (hipStream_t)stream, a);
-    FCN_CHECK_LAUNCH();
-    return 0;
+    if (!d || d->random_flip || d->random_shift) return FCN_E_BADARG;
+    return inp_first_stage(inp_view(d, 5), false, raw_pts, pt_off, nullptr, choice, frustum_angle, box2d, nullptr, K, Rtilt,
+                           nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, point_cloud, center_ref, nullptr, nullptr, nullptr,
+                           nullptr, rot_angle, nullptr, stream);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -317,26 +332,18 @@ __global__ __launch_bounds__(INP_T) void prepare_inputs_refine_kernel(InpRefineA
     const double c = cos(rot), s = sin(rot);
     const bool train = a.corners != nullptr;
     const bool flip = train && a.d.random_flip && a.coin[b] > 0.5;
-    double cx = 0.0, cy = 0.0, cz = 0.0, ang = 0.0, sl = 0.0, sw = 0.0, sh = 0.0, shift = 0.0;
+    InpBox k = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    double shift = 0.0;
     if (train) {
-        const double *cr = a.corners + (int64_t)b * 24;
-        const double dx = (cr[0] + cr[18]) / 2.0 - pcx, dy = (cr[1] + cr[19]) / 2.0 - pcy, dz = (cr[2] + cr[20]) / 2.0 - pcz;
-        cx = dx * c + dz * (-s); cy = dy; cz = dx * s + dz * c;
-        ang = a.heading[b] - rot;
-        if (flip) { cx = -cx; ang = M_PI - ang; }
-        sl = a.size[3 * b]; sw = a.size[3 * b + 1]; sh = a.size[3 * b + 2];
+        inp_label_box(k, a, b, pcx, pcy, pcz, rot, c, s, flip);
         if (a.d.random_shift) {
-            const double dist = sqrt(sl * sl + sw * sw), s1 = a.d.stride[0];
+            const double dist = sqrt(k.sl * k.sl + k.sw * k.sw), s1 = a.d.stride[0];
             shift = fmin(fmax(a.normal[b] * dist * 0.1, -2.0 * s1), 2.0 * s1);
-            cz += shift;
+            k.cz += shift;
         }
     }
     if (tid == 0) {
-        if (train) {
-            a.center[3 * b] = (float)cx; a.center[3 * b + 1] = (float)cy; a.center[3 * b + 2] = (float)cz;
-            a.head[b] = (float)ang;
-            a.osize[3 * b] = (float)sl; a.osize[3 * b + 1] = (float)sw; a.osize[3 * b + 2] = (float)sh;
-        }
+        if (train) inp_store_box(k, a, b);
         a.rot[b] = (float)rot;
         a.refc[3 * b] = (float)pcx; a.refc[3 * b + 1] = (float)pcy; a.refc[3 * b + 2] = (float)pcz;
     }
@@ -357,7 +364,7 @@ __global__ __launch_bounds__(INP_T) void prepare_inputs_refine_kernel(InpRefineA
     // ---- window centres over the predicted box's depth extent, edge-padded to Lpad; labels on stride 2
     const double w = a.pred_size[3 * b + 1];
     const double z1 = -w / 2.0, z2 = w / 2.0;
-    const double ca = cos(ang), sa = sin(ang);
+    const double ca = cos(k.ang), sa = sin(k.ang);
     double best = 1e300;
     int bidx = 0x7fffffff;
     bool any1 = false;
@@ -376,33 +383,13 @@ __global__ __launch_bounds__(INP_T) void prepare_inputs_refine_kernel(InpRefineA
             const double xr = flip ? -0.0 : 0.0;
             float *o = a.ref[sc] + (int64_t)b * 3 * Lp;
             o[l] = (float)xr; o[Lp + l] = 0.f; o[2 * Lp + l] = (float)z;
-            if (sc == 1 && a.cls && l < Lb) {
-                const double dx = xr - cx, dy = 0.0 - cy, dz = z - cz;
-                const bool in1 = inp_in_box(dx, dy, dz, ca, sa, sl * 0.3, sw * 0.3, sh * 0.3);
-                const bool in2 = inp_in_box(dx, dy, dz, ca, sa, sl * 0.6, sw * 0.6, sh * 0.6);
-                a.cls[(int64_t)b * Lp + l] = in1 ? 1 : (in2 ? -1 : 0);
-                any1 = any1 || in1;
-                const double dd = sqrt(dx * dx + dy * dy + dz * dz);
-                if (dd < best) { best = dd; bidx = l; }
-            }
+            if (sc == 1 && a.cls && l < Lb)                             // the real windows; the label box scaled by 0.3 / 0.6
+                inp_classify(a, b, Lp, l, xr, 0.0, z, k, ca, sa, 0.3, 0.6, any1, best, bidx);
         }
     }
     if (!a.cls) return;
-    if (any1) sany = 1;
-    sdist[tid] = best; sidx[tid] = bidx;
-    __syncthreads();
-    if (!sany) {
-        for (int o = INP_T / 2; o > 0; o >>= 1) {
-            if (tid < o) {
-                const double d2 = sdist[tid + o];
-                const int i2 = sidx[tid + o];
-                if (d2 < sdist[tid] || (d2 == sdist[tid] && i2 < sidx[tid])) { sdist[tid] = d2; sidx[tid] = i2; }
-            }
-            __syncthreads();
-        }
-        if (tid == 0 && sidx[0] != 0x7fffffff) a.cls[(int64_t)b * a.d.Lpad[1] + sidx[0]] = 1;
-    }
-    __syncthreads();
+    inp_nearest_positive(a, b, a.d.Lpad[1], sdist, sidx, &sany, tid, any1, best, bidx);
+    __syncthreads();                                                    // thread 0's positive, before the padding reads it
     __threadfence_block();
     // edge padding of the labels: positions >= L_b repeat the last real one
     {
@@ -432,8 +419,7 @@ extern "C" int fcn_prepare_inputs_refine(const fcn_inp_refine_desc *d, const flo
     if (train && (!heading || !size || !box3d_center || !box3d_heading || !box3d_size)) return FCN_E_BADARG;
     if (!train && cls_label) return FCN_E_BADARG;
     if (train && ((d->random_flip && !coin) || (d->random_shift && !normal))) return FCN_E_BADARG;
-    for (int s = 0; s < 4; ++s)
-        if (d->Lpad[s] <= 0 || !(d->stride[s] > 0.0) || !center_ref[s]) return FCN_E_BADARG;
+    if (!inp_scales_ok(4, d->Lpad, d->stride, center_ref)) return FCN_E_BADARG;
     InpRefineArgs a;
     a.d = *d; a.raw = raw_pts; a.off = pt_off; a.choice = choice; a.pred_corners = pred_corners; a.pred_angle = pred_angle;
     a.pred_size = pred_size; a.corners = box3d_corners; a.heading = heading; a.size = size; a.coin = coin; a.normal = normal;

@@ -132,57 +132,106 @@ def _row_counts(off):
     return (off[1:] - off[:-1]).to(torch.int64).contiguous()
 
 
-class InputBuilder:
-    """npoints / strides / max_depth as cfg.DATA.{NUM_SAMPLES, STRIDE, MAX_DEPTH}; one_hot over the dataset's classes."""
+# ---- what the three builders share
+def _need_device(device):
+    """The refusal of every public entry method of the builders off the GPU."""
+    if device.type != "cuda":
+        raise RuntimeError("frustum_convnet_amd: input construction is a HIP kernel (MI355X only); no CPU fallback")
+
+
+def _up(a, dev):
+    return torch.from_numpy(np.ascontiguousarray(a)).to(dev, non_blocking=True)
+
+
+def _ptr(x):
+    return None if x is None else x.data_ptr()
+
+
+def _pack(records, counts, fields):
+    """Host records as the arrays ONE upload each hands a launch: raw (sum n, pt_stride) float32 -- the records' points end to end
+    --, off (B+1) int64 and, per (name, record key, shape) of `fields`, the (B, *shape) float64 stack of that key."""
+    h = {"raw": np.concatenate([np.ascontiguousarray(r["points"], dtype=np.float32) for r in records], 0),
+         "off": np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)}
+    h.update(_stacks(records, fields))
+    return h
+
+
+def _stacks(records, fields):
+    return {name: np.stack([np.asarray(r[key], dtype=np.float64).reshape(shape) for r in records]) for name, key, shape in fields}
+
+
+def _class_rows(b, d, names, size_class=True):
+    """Into d, uploaded: size_class (B,1) int64, the class names' indices in builder b's table, and -- where b has one_hot -- their
+    one-hot rows (B, classes) float32.  The names are looked up (an unknown one raises ValueError) only where one of the two is
+    written: an inference batch without one_hot takes any name."""
+    if not (size_class or b.one_hot):
+        return
+    idx = [b.classes.index(n) for n in names]
+    if size_class:
+        d["size_class"] = torch.tensor(idx, dtype=torch.int64).view(len(idx), 1).to(b.device, non_blocking=True)
+    if b.one_hot:
+        oh = np.zeros((len(idx), len(b.classes)), dtype=np.float32)
+        oh[np.arange(len(idx)), idx] = 1.0
+        d["one_hot"] = _up(oh, b.device)
+
+
+def _desc_refs(desc, B, N, pt_stride, L, strides, out, *tail):
+    """A launch's descriptor (desc: its ctypes class; tail: the fields behind the strides) and the pointer array of out's center_ref*."""
+    n = len(strides)
+    refs = (ctypes.c_void_p * n)(*[out["center_ref%d" % (s + 1)].data_ptr() for s in range(n)])
+    return desc(B, N, pt_stride, (ctypes.c_int32 * n)(*L), (ctypes.c_double * n)(*strides), *tail), refs
+
+
+def _record(t, dev):
+    """The tensors of t are read by the kernel just enqueued on the current stream."""
+    for v in t.values():
+        if isinstance(v, torch.Tensor):
+            v.record_stream(torch.cuda.current_stream(dev))
+
+
+class _FirstStageBuilder:
+    """The first stage's builder at NSC strides: InputBuilder and SunrgbdInputBuilder are this class with their parameters --
+    DESC (the descriptor), ENTRY / ENTRY_INFER (the C entries), DATASET (the class table; None: cfg.DATA.DATASET_NAME), CALIB (per
+    calibration matrix: its key in t, its key in a record, its shape there), DRAW (the reference's draws) and DRAW_KEYS (their keys
+    in t) -- and with what is their own: how the boxes of a device selection are skipped, drawn for and calibrated."""
 
     def __init__(self, npoints, strides=None, max_depth=None, random_flip=False, random_shift=False, one_hot=True,
                  device="cuda"):
         self.npoints = int(npoints)
         self.strides = tuple(float(s) for s in (cfg.DATA.STRIDE if strides is None else strides))
         self.max_depth = float(cfg.DATA.MAX_DEPTH if max_depth is None else max_depth)
-        assert len(self.strides) == 4
+        assert len(self.strides) == self.NSC
         self.L = [len(np.arange(0, self.max_depth, s)) for s in self.strides]
         self.random_flip, self.random_shift, self.one_hot = bool(random_flip), bool(random_shift), bool(one_hot)
         self.device = torch.device(device)
-        self.classes = DATASET_INFO[cfg.DATA.DATASET_NAME].CLASSES
+        self.classes = DATASET_INFO[self.DATASET or cfg.DATA.DATASET_NAME].CLASSES
 
     def build(self, records, draws=None, with_seg=True):
         """records: list of dicts with RECORD_KEYS (points (n,>=3) float32 in rect camera coordinates, seg (n,), box2d (4,),
-        P (3,4), box3d (8,3) corners, heading, size (l,w,h), frustum_angle, type).  draws: (choice (B,N) int32, coin (B),
-        normal (B)) -- host arrays, or device tensors used as they are -- a DeviceDraws to draw on the device, or None to draw like
-        the reference (here and wherever a builder takes `draws`).  Returns the batch dict on the device.
-        = upload() (host -> device copies of the raw records and the draws) + launch() (the kernel)."""
-        return self.launch(self.upload(records, draws, with_seg))
+        P (3,4), box3d (8,3) corners, heading, size (l,w,h), frustum_angle, type); SUN-RGBD: K, Rtilt for P, see the class.
+        draws: (choice (B,N) int32, coin (B), normal (B)[, hshift (B)]) -- host arrays, or device tensors used as they are -- a
+        DeviceDraws to draw on the device, or None to draw like the reference (here and wherever a builder takes `draws`).  Returns
+        the batch dict on the device.
+        = the upload (host -> device copies of the raw records and the draws) + launch() (the kernel)."""
+        return self.launch(self._upload(records, draws, with_seg))
 
-    def upload(self, records, draws=None, with_seg=True):
-        """The raw records of a batch and their random draws as device tensors (ONE packed point buffer): what a loader hands
-        the GPU.  The returned dict feeds launch() any number of times (a resident raw batch re-built every step: bench.py)."""
-        if self.device.type != "cuda":
-            raise RuntimeError("frustum_convnet_amd: input construction is a HIP kernel (MI355X only); no CPU fallback")
-        B, N = len(records), self.npoints
+    def _upload(self, records, draws, with_seg):
+        """The raw records of a batch and their random draws as device tensors (ONE packed point buffer): launch()'s `t`."""
+        _need_device(self.device)
+        B, N, dev = len(records), self.npoints, self.device
         counts = [len(r["points"]) for r in records]
         if draws is None:
-            draws = draw(counts, N, self.random_flip, self.random_shift)
-        stride = int(records[0]["points"].shape[1])
-        raw = np.concatenate([np.ascontiguousarray(r["points"], dtype=np.float32) for r in records], 0)
-        off = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
-        f64 = lambda k, shape: np.stack([np.asarray(r[k], dtype=np.float64).reshape(shape) for r in records])
-        dev = self.device
-        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev, non_blocking=True)
-        t = {"raw": up(raw), "off": up(off),
-             "fangle": up(f64("frustum_angle", ())), "box2d": up(f64("box2d", (4,))), "P": up(f64("P", (12,))),
-             "corners": up(f64("box3d", (24,))), "heading": up(f64("heading", ())), "size": up(f64("size", (3,)))}
+            draws = self.DRAW(counts, N, self.random_flip, self.random_shift)
+        pt_stride = int(records[0]["points"].shape[1])
+        fields = (("fangle", "frustum_angle", ()), ("box2d", "box2d", (4,))) + self.CALIB + (
+            ("corners", "box3d", (24,)), ("heading", "heading", ()), ("size", "size", (3,)))
+        t = {k: _up(v, dev) for k, v in _pack(records, counts, fields).items()}
         if isinstance(draws, DeviceDraws):          # drawn on the device from the uploaded offsets (re-draw into these any time)
-            draws = draws.draw(_row_counts(t["off"]), N, self.random_flip, self.random_shift)
-        t["choice"], t["coin"], t["normal"] = _draw_tensors(draws, dev, 3)
-        t["seg"] = up(np.concatenate([np.asarray(r["seg"]).astype(np.int64) for r in records], 0)) if with_seg else None
-        size_class = [self.classes.index(r["type"]) for r in records]
-        t["size_class"] = torch.tensor(size_class, dtype=torch.int64).view(B, 1).to(dev, non_blocking=True)
-        if self.one_hot:
-            oh = np.zeros((B, len(self.classes)), dtype=np.float32)
-            oh[np.arange(B), size_class] = 1.0
-            t["one_hot"] = up(oh)
-        t["B"], t["pt_stride"] = B, stride
+            draws = draws.draw(_row_counts(t["off"]), N, self.random_flip, self.random_shift, hshift=len(self.DRAW_KEYS) == 4)
+        t.update(zip(self.DRAW_KEYS, _draw_tensors(draws, dev, len(self.DRAW_KEYS))))
+        t["seg"] = _up(np.concatenate([np.asarray(r["seg"]).astype(np.int64) for r in records], 0), dev) if with_seg else None
+        _class_rows(self, t, [r["type"] for r in records])
+        t["B"], t["pt_stride"] = B, pt_stride
         return t
 
     def alloc(self, B, with_seg=True):
@@ -193,39 +242,110 @@ class InputBuilder:
                "cls_label": torch.empty((B, self.L[1]), dtype=torch.int64, device=dev),
                "box3d_center": torch.empty((B, 3), **f32), "box3d_heading": torch.empty((B, 1), **f32),
                "box3d_size": torch.empty((B, 3), **f32)}
-        for s in range(4):
+        for s in range(self.NSC):
             out["center_ref%d" % (s + 1)] = torch.empty((B, 3, self.L[s]), **f32)
         if with_seg:
             out["seg_label"] = torch.empty((B, N), dtype=torch.int64, device=dev)
         return out
 
     def launch(self, t, out=None):
-        """ONE kernel launch on the current stream: uploaded records `t` -> the batch dict (into `out` when given: capturable
-        into a hipGraph, no allocation, no host work besides the call).  size_class / one_hot are the uploaded tensors."""
-        B, N = t["B"], self.npoints
+        """ONE kernel launch on the current stream: device tensors `t` -- raw, off, seg (or None), choice, fangle, box2d, the
+        calibration (P; SUN-RGBD: K, R), corners, heading, size, coin, normal (, hshift), size_class (, one_hot), B, pt_stride: the
+        uploaded records -- -> the batch dict (into `out` when given: capturable into a hipGraph, no allocation, no host work besides
+        the call).  size_class / one_hot are t's tensors."""
         dev = self.device
         if out is None:
-            out = self.alloc(B, with_seg=t["seg"] is not None)
-        desc = InpDesc(B, N, t["pt_stride"], (ctypes.c_int32 * 4)(*self.L), (ctypes.c_double * 4)(*self.strides), self.max_depth,
-                       1 if self.random_flip else 0, 1 if self.random_shift else 0)
-        refs = (ctypes.c_void_p * 4)(*[out["center_ref%d" % (s + 1)].data_ptr() for s in range(4)])
-        p = lambda x: None if x is None else x.data_ptr()
-        L = _native.lib()
+            out = self.alloc(t["B"], with_seg=t["seg"] is not None)
+        desc, refs = _desc_refs(self.DESC, t["B"], self.npoints, t["pt_stride"], self.L, self.strides, out, self.max_depth,
+                                1 if self.random_flip else 0, 1 if self.random_shift else 0)
+        ins = ("raw", "off", "seg", "choice", "fangle", "box2d") + tuple(c[0] for c in self.CALIB) + (
+            "corners", "heading", "size") + self.DRAW_KEYS[1:]
+        outs = ("cls_label", "box3d_center", "box3d_heading", "box3d_size", "rot_angle")
         with torch.cuda.device(dev):
-            _native.check(L.fcn_prepare_inputs(ctypes.byref(desc), p(t["raw"]), p(t["off"]), p(t["seg"]), p(t["choice"]),
-                                               p(t["fangle"]), p(t["box2d"]), p(t["P"]), p(t["corners"]), p(t["heading"]),
-                                               p(t["size"]), p(t["coin"]), p(t["normal"]), p(out["point_cloud"]), refs,
-                                               p(out["cls_label"]), p(out["box3d_center"]), p(out["box3d_heading"]),
-                                               p(out["box3d_size"]), p(out["rot_angle"]),
-                                               p(out.get("seg_label")) if t["seg"] is not None else None,
-                                               _native.current_stream(dev)), "fcn_prepare_inputs")
-        for v in t.values():                       # the uploads are read by the kernel just enqueued
-            if isinstance(v, torch.Tensor):
-                v.record_stream(torch.cuda.current_stream(dev))
+            _native.check(getattr(_native.lib(), self.ENTRY)(
+                ctypes.byref(desc), *[_ptr(t[k]) for k in ins], _ptr(out["point_cloud"]), refs, *[_ptr(out[k]) for k in outs],
+                _ptr(out.get("seg_label")) if t["seg"] is not None else None, _native.current_stream(dev)), self.ENTRY)
+        _record(t, dev)                            # the uploads are read by the kernel just enqueued
         out["size_class"] = t["size_class"]
         if "one_hot" in t:
             out["one_hot"] = t["one_hot"]
         return out
+
+    def alloc_infer(self, B):
+        """Output tensors of launch_infer() for a batch of B frustums: the dict of build_device() without 'kept' -- point_cloud,
+        rot_angle, center_ref1..NSC, rgb_prob (B,1) and, with one_hot, one_hot (B, classes), both zeros for the caller to fill."""
+        dev, N = self.device, self.npoints
+        f32 = dict(dtype=torch.float32, device=dev)
+        out = {"point_cloud": torch.empty((B, 3, N), **f32), "rot_angle": torch.empty((B, 1), **f32)}
+        for s in range(self.NSC):
+            out["center_ref%d" % (s + 1)] = torch.empty((B, 3, self.L[s]), **f32)
+        out["rgb_prob"] = torch.zeros((B, 1), **f32)
+        if self.one_hot:
+            out["one_hot"] = torch.zeros((B, len(self.classes)), **f32)
+        return out
+
+    def launch_infer(self, t, out):
+        """ONE launch of ENTRY_INFER on the current stream: device tensors `t` -- raw, off, choice (SUN-RGBD: indices into the full
+        packed selection), fangle, box2d, the calibration (P; SUN-RGBD: K, R), B, pt_stride -- into the caller-owned `out` of
+        alloc_infer(): no allocation, no host work besides the call (capturable into a hipGraph).  rgb_prob / one_hot are the
+        caller's to write.  Returns out."""
+        dev = self.device
+        desc, refs = _desc_refs(self.DESC, t["B"], self.npoints, t["pt_stride"], self.L, self.strides, out, self.max_depth, 0, 0)
+        ins = ("raw", "off", "choice", "fangle", "box2d") + tuple(c[0] for c in self.CALIB)
+        with torch.cuda.device(dev):
+            _native.check(getattr(_native.lib(), self.ENTRY_INFER)(
+                ctypes.byref(desc), *[t[k].data_ptr() for k in ins], out["point_cloud"].data_ptr(), refs, out["rot_angle"].data_ptr(),
+                _native.current_stream(dev)), self.ENTRY_INFER)
+        return out
+
+    def _calib(self, box_frame, *mats):
+        """The frames' calibration matrices (CALIB's, in its order) gathered per box through box_frame: {key in t: (B, 12 or 9) float64}."""
+        idx = box_frame.to(torch.int64)
+        return {k: torch.as_tensor(m).to(device=self.device, dtype=torch.float64).reshape((-1,) + shape).index_select(0, idx).contiguous()
+                for (k, _, shape), m in zip(self.CALIB, mats)}
+
+    def _picker(self, kept):
+        """x -> the rows `kept` (host indices) of a device tensor."""
+        idx = _up(kept, self.device)
+        return lambda x: x.index_select(0, idx).contiguous()
+
+    def _infer(self, sel, kept, pick, choice, calib, types, prob):
+        """What build_device() does once it knows the survivors `kept`, their choice table and calibration rows: ONE launch of
+        ENTRY_INFER through alloc_infer() / launch_infer(), the 2-D scores and the one-hot rows, 'kept'."""
+        B = len(kept)
+        t = dict(calib, raw=sel["points"], choice=choice, off=pick(sel["off"]),      # (the kernel reads a sample's first row only)
+                 fangle=pick(sel["frustum_angle"]), box2d=pick(sel["box2d"]))
+        out = self.launch_infer(dict(t, B=B, pt_stride=int(sel["points"].shape[1])), self.alloc_infer(B))
+        _record(t, self.device)
+        out["rgb_prob"] = _up(np.asarray(prob, dtype=np.float32)[kept].reshape(B, 1), self.device)
+        _class_rows(self, out, [types[i] for i in kept], size_class=False)
+        out["kept"] = kept
+        return out
+
+    def _train(self, sel, kept, drawn, calib, types, with_seg, out=None):
+        """What build_device_train() does once it has the draws' device tensors `drawn` (DRAW_KEYS' order) and the calibration rows:
+        the selection as launch()'s `t`, ONE launch of ENTRY."""
+        K = len(kept)
+        t = {"raw": sel["points"], "off": sel["off"], "seg": sel["seg"] if with_seg else None, "fangle": sel["frustum_angle"],
+             "box2d": sel["box2d"], "corners": sel["box3d"].reshape(K, 24), "heading": sel["heading"], "size": sel["size"]}
+        t.update(calib)
+        t.update(zip(self.DRAW_KEYS, drawn))
+        _class_rows(self, t, [types[i] for i in kept])
+        t["B"], t["pt_stride"] = K, int(sel["points"].shape[1])
+        return self.launch(t, out)
+
+
+class InputBuilder(_FirstStageBuilder):
+    """npoints / strides / max_depth as cfg.DATA.{NUM_SAMPLES, STRIDE, MAX_DEPTH}; one_hot over the dataset's classes."""
+    NSC, DESC, DATASET = 4, InpDesc, None
+    ENTRY, ENTRY_INFER = "fcn_prepare_inputs", "fcn_prepare_inputs_infer"
+    CALIB = (("P", "P", (12,)),)
+    DRAW, DRAW_KEYS = staticmethod(draw), ("choice", "coin", "normal")
+
+    def upload(self, records, draws=None, with_seg=True):
+        """The raw records of a batch and their random draws as device tensors (ONE packed point buffer): what a loader hands
+        the GPU.  The returned dict feeds launch() any number of times (a resident raw batch re-built every step: bench.py)."""
+        return self._upload(records, draws, with_seg)
 
     def build_device(self, sel, P, types, prob, draws=None, img_height_threshold=5, lidar_point_threshold=1):
         """The first stage's inference batch (the reference's from_rgb_detection dict, provider_sample.py:184-195: point_cloud,
@@ -235,9 +355,8 @@ class InputBuilder:
         int32, ...) for the B surviving boxes, or None to draw like draw() from their counts (no flip, no shift: inference).
         A box is dropped when ymax - ymin < img_height_threshold, xmax - xmin < 1 or count < lidar_point_threshold
         (prepare_data.py:546-548; a box without a point cannot be resampled and is dropped in any case); 'kept' (B,) int64 (host) lists the survivors' box indices.  The host reads the D boxes here.
-        With no survivor the dict holds 'kept' alone."""
-        if self.device.type != "cuda":
-            raise RuntimeError("frustum_convnet_amd: input construction is a HIP kernel (MI355X only); no CPU fallback")
+        ONE launch of fcn_prepare_inputs_infer.  With no survivor the dict holds 'kept' alone."""
+        _need_device(self.device)
         counts = np.asarray(sel["counts"], dtype=np.int64)
         D, N = len(counts), self.npoints
         if len(types) != D or len(prob) != D:
@@ -245,71 +364,14 @@ class InputBuilder:
         box = sel["box2d"].cpu().numpy().reshape(D, 4)                        # D boxes: the skip rules
         skip = (box[:, 3] - box[:, 1] < img_height_threshold) | (box[:, 2] - box[:, 0] < 1) | (counts < lidar_point_threshold)
         kept = np.nonzero(~skip & (counts > 0))[0]
-        B = len(kept)
-        if B == 0:
+        if len(kept) == 0:
             return {"kept": kept}
         if draws is None:
             draws = draw(counts[kept], N, False, False)
-        dev = self.device
-        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev, non_blocking=True)
-        idx = up(kept)
-        pick = lambda x: x.index_select(0, idx).contiguous()
+        pick = self._picker(kept)
         if isinstance(draws, DeviceDraws):
             draws = draws.draw(pick(_row_counts(sel["off"])), N, False, False)
-        Pd = torch.as_tensor(P).to(device=dev, dtype=torch.float64).reshape(-1, 12)
-        t = {"raw": sel["points"], "choice": _draw_tensors(draws, dev, 1)[0],
-             "off": pick(sel["off"]),                                         # the kernel reads a sample's first row only
-             "fangle": pick(sel["frustum_angle"]), "box2d": pick(sel["box2d"]),
-             "P": Pd.index_select(0, pick(sel["box_frame"]).to(torch.int64)).contiguous()}
-        f32 = dict(dtype=torch.float32, device=dev)
-        out = {"point_cloud": torch.empty((B, 3, N), **f32), "rot_angle": torch.empty((B, 1), **f32)}
-        for s in range(4):
-            out["center_ref%d" % (s + 1)] = torch.empty((B, 3, self.L[s]), **f32)
-        desc = InpDesc(B, N, int(sel["points"].shape[1]), (ctypes.c_int32 * 4)(*self.L), (ctypes.c_double * 4)(*self.strides),
-                       self.max_depth, 0, 0)
-        refs = (ctypes.c_void_p * 4)(*[out["center_ref%d" % (s + 1)].data_ptr() for s in range(4)])
-        p = lambda x: x.data_ptr()
-        with torch.cuda.device(dev):
-            _native.check(_native.lib().fcn_prepare_inputs_infer(
-                ctypes.byref(desc), p(t["raw"]), p(t["off"]), p(t["choice"]), p(t["fangle"]), p(t["box2d"]), p(t["P"]),
-                p(out["point_cloud"]), refs, p(out["rot_angle"]), _native.current_stream(dev)), "fcn_prepare_inputs_infer")
-        for v in t.values():
-            v.record_stream(torch.cuda.current_stream(dev))
-        out["rgb_prob"] = up(np.asarray(prob, dtype=np.float32)[kept].reshape(B, 1))
-        if self.one_hot:
-            oh = np.zeros((B, len(self.classes)), dtype=np.float32)
-            oh[np.arange(B), [self.classes.index(types[i]) for i in kept]] = 1.0
-            out["one_hot"] = up(oh)
-        out["kept"] = kept
-        return out
-
-    def alloc_infer(self, B):
-        """Output tensors of launch_infer() for a batch of B frustums: the dict of build_device() without 'kept' -- point_cloud,
-        rot_angle, center_ref1..4, rgb_prob (B,1) and, with one_hot, one_hot (B, classes), both zeros for the caller to fill."""
-        dev, N = self.device, self.npoints
-        f32 = dict(dtype=torch.float32, device=dev)
-        out = {"point_cloud": torch.empty((B, 3, N), **f32), "rot_angle": torch.empty((B, 1), **f32)}
-        for s in range(4):
-            out["center_ref%d" % (s + 1)] = torch.empty((B, 3, self.L[s]), **f32)
-        out["rgb_prob"] = torch.zeros((B, 1), **f32)
-        if self.one_hot:
-            out["one_hot"] = torch.zeros((B, len(self.classes)), **f32)
-        return out
-
-    def launch_infer(self, t, out):
-        """ONE launch of fcn_prepare_inputs_infer on the current stream: device tensors `t` -- raw, off, choice, fangle, box2d, P,
-        B, pt_stride -- into the caller-owned `out` of alloc_infer(): no allocation, no host work besides the call (capturable into
-        a hipGraph).  rgb_prob / one_hot are the caller's to write.  Returns out."""
-        dev = self.device
-        desc = InpDesc(t["B"], self.npoints, t["pt_stride"], (ctypes.c_int32 * 4)(*self.L), (ctypes.c_double * 4)(*self.strides),
-                       self.max_depth, 0, 0)
-        refs = (ctypes.c_void_p * 4)(*[out["center_ref%d" % (s + 1)].data_ptr() for s in range(4)])
-        p = lambda x: x.data_ptr()
-        with torch.cuda.device(dev):
-            _native.check(_native.lib().fcn_prepare_inputs_infer(
-                ctypes.byref(desc), p(t["raw"]), p(t["off"]), p(t["choice"]), p(t["fangle"]), p(t["box2d"]), p(t["P"]),
-                p(out["point_cloud"]), refs, p(out["rot_angle"]), _native.current_stream(dev)), "fcn_prepare_inputs_infer")
-        return out
+        return self._infer(sel, kept, pick, _draw_tensors(draws, self.device, 1)[0], self._calib(pick(sel["box_frame"]), P), types, prob)
 
     def build_device_train(self, sel, P, types, draws=None, with_seg=True, out=None):
         """The first stage's TRAINING batch -- the dict of build(), same keys, shapes and dtypes -- straight from the device
@@ -318,32 +380,15 @@ class InputBuilder:
         frustum_training_candidates was given (the kept ones are looked up through sel["kept"]); draws: (choice (K,N) int32,
         coin (K), normal (K)) for the K kept boxes, or None to draw like the reference from their counts; out: launch()'s.
         ONE launch of fcn_prepare_inputs.  With no kept box the dict holds 'kept' alone."""
-        if self.device.type != "cuda":
-            raise RuntimeError("frustum_convnet_amd: input construction is a HIP kernel (MI355X only); no CPU fallback")
+        _need_device(self.device)
         kept = np.asarray(sel["kept"], dtype=np.int64)
-        K = len(kept)
-        if K == 0:
+        if len(kept) == 0:
             return {"kept": kept}
         if draws is None:
             draws = draw(sel["counts"], self.npoints, self.random_flip, self.random_shift)
-        dev = self.device
         if isinstance(draws, DeviceDraws):
             draws = draws.draw(_row_counts(sel["off"]), self.npoints, self.random_flip, self.random_shift)
-        choice, coin, normal = _draw_tensors(draws, dev, 3)
-        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev, non_blocking=True)
-        Pd = torch.as_tensor(P).to(device=dev, dtype=torch.float64).reshape(-1, 12)
-        t = {"raw": sel["points"], "off": sel["off"], "seg": sel["seg"] if with_seg else None,
-             "choice": choice, "fangle": sel["frustum_angle"], "box2d": sel["box2d"],
-             "P": Pd.index_select(0, sel["box_frame"].to(torch.int64)).contiguous(), "corners": sel["box3d"].reshape(K, 24),
-             "heading": sel["heading"], "size": sel["size"], "coin": coin, "normal": normal}
-        size_class = [self.classes.index(types[i]) for i in kept]
-        t["size_class"] = torch.tensor(size_class, dtype=torch.int64).view(K, 1).to(dev, non_blocking=True)
-        if self.one_hot:
-            oh = np.zeros((K, len(self.classes)), dtype=np.float32)
-            oh[np.arange(K), size_class] = 1.0
-            t["one_hot"] = up(oh)
-        t["B"], t["pt_stride"] = K, int(sel["points"].shape[1])
-        return self.launch(t, out)
+        return self._train(sel, kept, _draw_tensors(draws, self.device, 3), self._calib(sel["box_frame"], P), types, with_seg, out)
 
     def algorithmic_bytes(self, B, with_seg=True, pt_stride=4):
         """HBM bytes one launch has to move (the roofline's numerator): per frustum N gathered raw points + their draw indices
@@ -367,99 +412,15 @@ def draw_sunrgbd(counts, npoints, random_flip=True, random_shift=True, rng=np.ra
     return np.stack(choice).astype(np.int32), f(coin), f(normal), f(hshift)
 
 
-class SunrgbdInputBuilder:
+class SunrgbdInputBuilder(_FirstStageBuilder):
     """Batch construction of datasets/provider_sample_sunrgbd.py::ProviderDataset (+ default_collate) on the device: five
     strides, window centres through the camera matrix K and the tilt rotation Rtilt.  Records: points (n,>=3) float32 in
     upright camera coordinates, seg (n,), box2d (4,), K (3,3), Rtilt (3,3), box3d (8,3), heading, size (l,w,h),
-    frustum_angle, type."""
-
-    def __init__(self, npoints, strides=None, max_depth=None, random_flip=False, random_shift=False, one_hot=True,
-                 device="cuda"):
-        self.npoints = int(npoints)
-        self.strides = tuple(float(s) for s in (cfg.DATA.STRIDE if strides is None else strides))
-        self.max_depth = float(cfg.DATA.MAX_DEPTH if max_depth is None else max_depth)
-        assert len(self.strides) == 5
-        self.L = [len(np.arange(0, self.max_depth, s)) for s in self.strides]
-        self.random_flip, self.random_shift, self.one_hot = bool(random_flip), bool(random_shift), bool(one_hot)
-        self.device = torch.device(device)
-        self.classes = DATASET_INFO["SUNRGBD"].CLASSES
-
-    def build(self, records, draws=None, with_seg=True):
-        """draws: (choice (B,N) int32, coin (B), normal (B), hshift (B)) or None to draw like the reference."""
-        if self.device.type != "cuda":
-            raise RuntimeError("frustum_convnet_amd: input construction is a HIP kernel (MI355X only); no CPU fallback")
-        B, N = len(records), self.npoints
-        counts = [len(r["points"]) for r in records]
-        if draws is None:
-            draws = draw_sunrgbd(counts, N, self.random_flip, self.random_shift)
-        stride = int(records[0]["points"].shape[1])
-        raw = np.concatenate([np.ascontiguousarray(r["points"], dtype=np.float32) for r in records], 0)
-        off = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
-        f64 = lambda k, shape: np.stack([np.asarray(r[k], dtype=np.float64).reshape(shape) for r in records])
-        dev = self.device
-        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev, non_blocking=True)
-        t = {"raw": up(raw), "off": up(off),
-             "fangle": up(f64("frustum_angle", ())), "box2d": up(f64("box2d", (4,))), "K": up(f64("K", (9,))),
-             "R": up(f64("Rtilt", (9,))), "corners": up(f64("box3d", (24,))), "heading": up(f64("heading", ())),
-             "size": up(f64("size", (3,)))}
-        if isinstance(draws, DeviceDraws):
-            draws = draws.draw(_row_counts(t["off"]), N, self.random_flip, self.random_shift, hshift=True)
-        t["choice"], t["coin"], t["normal"], t["hshift"] = _draw_tensors(draws, dev, 4)
-        t["seg"] = up(np.concatenate([np.asarray(r["seg"]).astype(np.int64) for r in records], 0)) if with_seg else None
-        self._classes(t, [self.classes.index(r["type"]) for r in records])
-        t["B"], t["pt_stride"] = B, stride
-        return self.launch(t)
-
-    def _classes(self, t, size_class):
-        """size_class (B,1) int64 and, with one_hot, its one-hot rows from a host list of class indices, uploaded into t."""
-        B = len(size_class)
-        t["size_class"] = torch.tensor(size_class, dtype=torch.int64).view(B, 1).to(self.device, non_blocking=True)
-        if self.one_hot:
-            oh = np.zeros((B, len(self.classes)), dtype=np.float32)
-            oh[np.arange(B), size_class] = 1.0
-            t["one_hot"] = torch.from_numpy(oh).to(self.device, non_blocking=True)
-
-    def alloc(self, B, with_seg=True):
-        """Output tensors of launch() for a batch of B frustums (pass as `out` to write the same buffers every step)."""
-        dev, N = self.device, self.npoints
-        f32 = dict(dtype=torch.float32, device=dev)
-        out = {"point_cloud": torch.empty((B, 3, N), **f32), "rot_angle": torch.empty((B, 1), **f32),
-               "cls_label": torch.empty((B, self.L[1]), dtype=torch.int64, device=dev),
-               "box3d_center": torch.empty((B, 3), **f32), "box3d_heading": torch.empty((B, 1), **f32),
-               "box3d_size": torch.empty((B, 3), **f32)}
-        for s in range(5):
-            out["center_ref%d" % (s + 1)] = torch.empty((B, 3, self.L[s]), **f32)
-        if with_seg:
-            out["seg_label"] = torch.empty((B, N), dtype=torch.int64, device=dev)
-        return out
-
-    def launch(self, t, out=None):
-        """ONE kernel launch on the current stream: device tensors `t` -- raw, off, seg (or None), choice, fangle, box2d, K, R,
-        corners, heading, size, coin, normal, hshift, size_class (, one_hot), B, pt_stride -- -> the batch dict (into `out` when
-        given: capturable into a hipGraph, no allocation, no host work besides the call).  size_class / one_hot are t's tensors."""
-        B, N = t["B"], self.npoints
-        dev = self.device
-        if out is None:
-            out = self.alloc(B, with_seg=t["seg"] is not None)
-        desc = Inp5Desc(B, N, t["pt_stride"], (ctypes.c_int32 * 5)(*self.L), (ctypes.c_double * 5)(*self.strides), self.max_depth,
-                        1 if self.random_flip else 0, 1 if self.random_shift else 0)
-        refs = (ctypes.c_void_p * 5)(*[out["center_ref%d" % (s + 1)].data_ptr() for s in range(5)])
-        p = lambda x: None if x is None else x.data_ptr()
-        with torch.cuda.device(dev):
-            _native.check(_native.lib().fcn_prepare_inputs_sunrgbd(
-                ctypes.byref(desc), p(t["raw"]), p(t["off"]), p(t["seg"]), p(t["choice"]), p(t["fangle"]), p(t["box2d"]),
-                p(t["K"]), p(t["R"]), p(t["corners"]), p(t["heading"]), p(t["size"]), p(t["coin"]), p(t["normal"]),
-                p(t["hshift"]), p(out["point_cloud"]), refs, p(out["cls_label"]), p(out["box3d_center"]),
-                p(out["box3d_heading"]), p(out["box3d_size"]), p(out["rot_angle"]),
-                p(out.get("seg_label")) if t["seg"] is not None else None,
-                _native.current_stream(dev)), "fcn_prepare_inputs_sunrgbd")
-        for v in t.values():                       # the uploads are read by the kernel just enqueued
-            if isinstance(v, torch.Tensor):
-                v.record_stream(torch.cuda.current_stream(dev))
-        out["size_class"] = t["size_class"]
-        if "one_hot" in t:
-            out["one_hot"] = t["one_hot"]
-        return out
+    frustum_angle, type.  draws: (choice (B,N) int32, coin (B), normal (B), hshift (B)) or None to draw like the reference."""
+    NSC, DESC, DATASET = 5, Inp5Desc, "SUNRGBD"
+    ENTRY, ENTRY_INFER = "fcn_prepare_inputs_sunrgbd", "fcn_prepare_inputs_sunrgbd_infer"
+    CALIB = (("K", "K", (9,)), ("R", "Rtilt", (9,)))
+    DRAW, DRAW_KEYS = staticmethod(draw_sunrgbd), ("choice", "coin", "normal", "hshift")
 
     def _compose(self, choice, sub):
         """The builder's draw through the reference's frustum subsample: choice (B,N) indexes the subsampled record where a box
@@ -474,27 +435,18 @@ class SunrgbdInputBuilder:
         """dd.draw over the records' rows with the frustum subsamples composed in the kernel: cnt (B,) the boxes' full row counts
         on the device, sub: per box the host's subsample indices or None -- packed and uploaded (a box without one draws from
         its cnt rows)."""
-        dev = self.device
         counts = cnt.to(torch.int64).contiguous()
         if all(ix is None for ix in sub):
             return dd.draw(counts, self.npoints, flip, shift, hshift=True)
         lens = [0 if ix is None else len(ix) for ix in sub]
-        sub_off = torch.from_numpy(np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)).to(dev, non_blocking=True)
-        flat = torch.from_numpy(np.concatenate([np.asarray(ix, dtype=np.int32) for ix in sub if ix is not None])).to(dev, non_blocking=True)
+        sub_off = _up(np.concatenate([[0], np.cumsum(lens)]).astype(np.int64), self.device)
+        flat = _up(np.concatenate([np.asarray(ix, dtype=np.int32) for ix in sub if ix is not None]), self.device)
         return dd.draw(counts, self.npoints, flip, shift, hshift=True, sub=flat, sub_off=sub_off)
 
     def _choice(self, draws, sub):
         """The choice table the kernel reads: a device tensor as it is -- indices into the full packed selection, as
         DeviceDraws writes them through `sub` -- a host table composed with the subsamples and uploaded."""
-        if _is_device_draws(draws):
-            return draws[0]
-        return torch.from_numpy(np.ascontiguousarray(self._compose(draws[0], sub))).to(self.device, non_blocking=True)
-
-    def _calib_rows(self, K, Rtilt, box_frame):
-        dev = self.device
-        idx = box_frame.to(torch.int64)
-        gather = lambda m: torch.as_tensor(m).to(device=dev, dtype=torch.float64).reshape(-1, 9).index_select(0, idx).contiguous()
-        return gather(K), gather(Rtilt)
+        return draws[0] if _is_device_draws(draws) else _up(self._compose(draws[0], sub), self.device)
 
     def build_device(self, sel, K, Rtilt, types, prob, draws=None, point_threshold=5):
         """The five-scale model's inference batch (the reference's from_rgb_detection dict, provider_sample_sunrgbd.py:165-186:
@@ -507,67 +459,20 @@ class SunrgbdInputBuilder:
         lists the survivors' box indices.  ONE launch of fcn_prepare_inputs_sunrgbd_infer, which gathers from the full packed
         selection through sub[choice].  With no survivor the dict holds 'kept' alone."""
         from .frustum import subsampled_counts
-        if self.device.type != "cuda":
-            raise RuntimeError("frustum_convnet_amd: input construction is a HIP kernel (MI355X only); no CPU fallback")
+        _need_device(self.device)
         D, N = len(sel["counts"]), self.npoints
         if len(types) != D or len(prob) != D:
             raise ValueError("build_device: %d boxes, %d types, %d prob" % (D, len(types), len(prob)))
         rows = subsampled_counts(sel["counts"], sel["sub"])
         kept = np.nonzero(rows >= max(1, int(point_threshold)))[0]
-        B = len(kept)
-        if B == 0:
+        if len(kept) == 0:
             return {"kept": kept}
         if draws is None:
             draws = draw_sunrgbd(rows[kept], N, False, False)
-        dev = self.device
-        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev, non_blocking=True)
-        idx = up(kept)
-        pick = lambda x: x.index_select(0, idx).contiguous()
+        pick, sub = self._picker(kept), [sel["sub"][d] for d in kept]
         if isinstance(draws, DeviceDraws):
-            draws = self._device_draw(draws, pick(sel["cnt"]), [sel["sub"][d] for d in kept], False, False)
-        Kd, Rd = self._calib_rows(K, Rtilt, pick(sel["box_frame"]))
-        t = {"raw": sel["points"], "choice": self._choice(draws, [sel["sub"][d] for d in kept]),
-             "off": pick(sel["off"]),                                         # the kernel reads a sample's first row only
-             "fangle": pick(sel["frustum_angle"]), "box2d": pick(sel["box2d"]), "K": Kd, "R": Rd}
-        out = self.launch_infer(dict(t, B=B, pt_stride=int(sel["points"].shape[1])), self.alloc_infer(B))
-        for v in t.values():
-            v.record_stream(torch.cuda.current_stream(dev))
-        out["rgb_prob"] = up(np.asarray(prob, dtype=np.float32)[kept].reshape(B, 1))
-        if self.one_hot:
-            oh = np.zeros((B, len(self.classes)), dtype=np.float32)
-            oh[np.arange(B), [self.classes.index(types[i]) for i in kept]] = 1.0
-            out["one_hot"] = up(oh)
-        out["kept"] = kept
-        return out
-
-    def alloc_infer(self, B):
-        """Output tensors of launch_infer() for a batch of B frustums: the dict of build_device() without 'kept' -- point_cloud,
-        rot_angle, center_ref1..5, rgb_prob (B,1) and, with one_hot, one_hot (B, classes), both zeros for the caller to fill."""
-        dev, N = self.device, self.npoints
-        f32 = dict(dtype=torch.float32, device=dev)
-        out = {"point_cloud": torch.empty((B, 3, N), **f32), "rot_angle": torch.empty((B, 1), **f32)}
-        for s in range(5):
-            out["center_ref%d" % (s + 1)] = torch.empty((B, 3, self.L[s]), **f32)
-        out["rgb_prob"] = torch.zeros((B, 1), **f32)
-        if self.one_hot:
-            out["one_hot"] = torch.zeros((B, len(self.classes)), **f32)
-        return out
-
-    def launch_infer(self, t, out):
-        """ONE launch of fcn_prepare_inputs_sunrgbd_infer on the current stream: device tensors `t` -- raw, off, choice (indices
-        into the full packed selection), fangle, box2d, K, R, B, pt_stride -- into the caller-owned `out` of alloc_infer(): no
-        allocation, no host work besides the call (capturable into a hipGraph).  rgb_prob / one_hot are the caller's to write.
-        Returns out."""
-        dev = self.device
-        desc = Inp5Desc(t["B"], self.npoints, t["pt_stride"], (ctypes.c_int32 * 5)(*self.L), (ctypes.c_double * 5)(*self.strides),
-                        self.max_depth, 0, 0)
-        refs = (ctypes.c_void_p * 5)(*[out["center_ref%d" % (s + 1)].data_ptr() for s in range(5)])
-        p = lambda x: x.data_ptr()
-        with torch.cuda.device(dev):
-            _native.check(_native.lib().fcn_prepare_inputs_sunrgbd_infer(
-                ctypes.byref(desc), p(t["raw"]), p(t["off"]), p(t["choice"]), p(t["fangle"]), p(t["box2d"]), p(t["K"]), p(t["R"]),
-                p(out["point_cloud"]), refs, p(out["rot_angle"]), _native.current_stream(dev)), "fcn_prepare_inputs_sunrgbd_infer")
-        return out
+            draws = self._device_draw(draws, pick(sel["cnt"]), sub, False, False)
+        return self._infer(sel, kept, pick, self._choice(draws, sub), self._calib(pick(sel["box_frame"]), K, Rtilt), types, prob)
 
     def build_device_train(self, sel, K, Rtilt, types, draws=None, with_seg=True):
         """The five-scale model's TRAINING batch -- the dict of build(), same keys, shapes and dtypes -- straight from the device
@@ -578,25 +483,16 @@ class SunrgbdInputBuilder:
         None to draw like the reference from the records' row counts.  ONE launch of fcn_prepare_inputs_sunrgbd, which gathers
         points and labels from the full packed selection through sub[choice].  With no kept box the dict holds 'kept' alone."""
         from .frustum import subsampled_counts
-        if self.device.type != "cuda":
-            raise RuntimeError("frustum_convnet_amd: input construction is a HIP kernel (MI355X only); no CPU fallback")
+        _need_device(self.device)
         kept = np.asarray(sel["kept"], dtype=np.int64)
-        B, N = len(kept), self.npoints
-        if B == 0:
+        if len(kept) == 0:
             return {"kept": kept}
         if draws is None:
-            draws = draw_sunrgbd(subsampled_counts(sel["counts"], sel["sub"]), N, self.random_flip, self.random_shift)
-        dev = self.device
+            draws = draw_sunrgbd(subsampled_counts(sel["counts"], sel["sub"]), self.npoints, self.random_flip, self.random_shift)
         if isinstance(draws, DeviceDraws):
             draws = self._device_draw(draws, sel["cnt"], sel["sub"], self.random_flip, self.random_shift)
-        coin, normal, hshift = _draw_tensors(draws, dev, 4)[1:]
-        Kd, Rd = self._calib_rows(K, Rtilt, sel["box_frame"])
-        t = {"raw": sel["points"], "off": sel["off"], "seg": sel["seg"] if with_seg else None, "choice": self._choice(draws, sel["sub"]),
-             "fangle": sel["frustum_angle"], "box2d": sel["box2d"], "K": Kd, "R": Rd, "corners": sel["box3d"].reshape(B, 24),
-             "heading": sel["heading"], "size": sel["size"], "coin": coin, "normal": normal, "hshift": hshift}
-        self._classes(t, [self.classes.index(types[i]) for i in kept])
-        t["B"], t["pt_stride"] = B, int(sel["points"].shape[1])
-        return self.launch(t)
+        drawn = (self._choice(draws, sel["sub"]),) + _draw_tensors(draws, self.device, 4)[1:]
+        return self._train(sel, kept, drawn, self._calib(sel["box_frame"], K, Rtilt), types, with_seg)
 
 
 def sunrgbd_records_from_fixture(g):
@@ -672,17 +568,13 @@ class RefineInputBuilder:
         psize; with labels also corners, heading, size, coin, normal) -> `out` (alloc(B, lpad, with_labels)).  No allocation, no
         host read: capturable into a hipGraph.  Returns `out`."""
         from ._native import InpRefineDesc
-        dev = self.device
-        B = int(out["point_cloud"].shape[0])
-        desc = InpRefineDesc(B, self.npoints, pt_stride, (ctypes.c_int32 * 4)(*lpad), (ctypes.c_double * 4)(*self.strides),
-                             1 if (self.random_flip and with_labels) else 0, 1 if (self.random_shift and with_labels) else 0)
-        refs = (ctypes.c_void_p * 4)(*[out["center_ref%d" % (s + 1)].data_ptr() for s in range(4)])
-        p = lambda x: None if x is None else x.data_ptr()
+        dev, p = self.device, _ptr
+        desc, refs = _desc_refs(InpRefineDesc, int(out["point_cloud"].shape[0]), self.npoints, pt_stride, lpad, self.strides, out,
+                                1 if (self.random_flip and with_labels) else 0, 1 if (self.random_shift and with_labels) else 0)
         lab = (lambda k: p(t.get(k))) if with_labels else (lambda k: None)
         olab = (lambda k: p(out.get(k))) if with_labels else (lambda k: None)
-        L = _native.lib()
         with torch.cuda.device(dev):
-            _native.check(L.fcn_prepare_inputs_refine(
+            _native.check(_native.lib().fcn_prepare_inputs_refine(
                 ctypes.byref(desc), p(t["raw"]), p(t["off"]), p(t["choice"]), p(t["pcorners"]), p(t["pangle"]), p(t["psize"]),
                 lab("corners"), lab("heading"), lab("size"), lab("coin"), lab("normal"),
                 p(out["point_cloud"]), refs, olab("cls_label"), olab("box3d_center"), olab("box3d_heading"),
@@ -693,8 +585,7 @@ class RefineInputBuilder:
     def _launch(self, t, B, pt_stride, Lpad, with_labels):
         """alloc() + launch() on the device tensors `t`: the part build(), build_device() and build_device_train() share."""
         out = self.launch(t, self.alloc(B, Lpad, with_labels), pt_stride, Lpad, with_labels)
-        for v in t.values():
-            v.record_stream(torch.cuda.current_stream(self.device))
+        _record(t, self.device)
         return out
 
     def _lpad(self, widths):
@@ -709,11 +600,6 @@ class RefineInputBuilder:
                                  "(fcn_prepare_inputs_refine needs every pred_size width > 0)" % (i, float(w)))
         return [int(max(len(np.arange(-w / 2.0, w / 2.0, s)) for w in widths)) for s in self.strides]
 
-    def _one_hot(self, size_class):
-        oh = np.zeros((len(size_class), len(self.classes)), dtype=np.float32)
-        oh[np.arange(len(size_class)), size_class] = 1.0
-        return torch.from_numpy(oh).to(self.device, non_blocking=True)
-
     def build_device(self, cands, types, prob=None, draws=None):
         """The inference batch (build(..., with_labels=False)) straight from the device tensors of cascade.refine_candidates:
         no point leaves the device.  cands: its dict (points, off, pred_box3d, pred_angle, pred_size, score on the device,
@@ -723,8 +609,7 @@ class RefineInputBuilder:
         Candidates without a point are dropped before the launch (prepare_data_refine.py:739-741, lidar_point_threshold = 1);
         'kept' (B,) int64 (host) lists the survivors' candidate indices.  The host reads D numbers here: the predicted widths,
         which decide the padded window counts.  With no survivor the dict holds 'kept' alone."""
-        if self.device.type != "cuda":
-            raise RuntimeError("frustum_convnet_amd: input construction is a HIP kernel (MI355X only); no CPU fallback")
+        _need_device(self.device)
         counts = np.asarray(cands["counts"], dtype=np.int64)
         D, N = len(counts), self.npoints
         if len(types) != D or (prob is not None and len(prob) != D):
@@ -736,9 +621,8 @@ class RefineInputBuilder:
         if draws is None:
             draws = draw_refine(counts[kept], N, False, False)
         dev = self.device
-        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev, non_blocking=True)
         widths = cands["pred_size"][:, 1].cpu().numpy()                       # D numbers: the tensor shapes depend on them
-        sel = None if B == D else up(kept)
+        sel = None if B == D else _up(kept, dev)
         pick = lambda x: x.contiguous() if sel is None else x.index_select(0, sel).contiguous()
         off = cands["off"]
         if isinstance(draws, DeviceDraws):
@@ -748,12 +632,11 @@ class RefineInputBuilder:
              "off": off if sel is None else torch.cat([off.index_select(0, sel), off[int(kept[-1]) + 1:int(kept[-1]) + 2]]),
              "pcorners": pick(cands["pred_box3d"]), "pangle": pick(cands["pred_angle"]), "psize": pick(cands["pred_size"])}
         out = self._launch(t, B, int(cands["points"].shape[1]), self._lpad(widths[kept]), False)
-        if self.one_hot:
-            out["one_hot"] = self._one_hot([self.classes.index(types[i]) for i in kept])
+        _class_rows(self, out, [types[i] for i in kept], size_class=False)
         if prob is None:
             out["rgb_prob"] = pick(cands["score"]).to(torch.float32).reshape(B, 1)
         else:
-            out["rgb_prob"] = up(np.asarray(prob, dtype=np.float32)[kept].reshape(B, 1))
+            out["rgb_prob"] = _up(np.asarray(prob, dtype=np.float32)[kept].reshape(B, 1), dev)
         out["kept"] = kept
         return out
 
@@ -764,8 +647,7 @@ class RefineInputBuilder:
         (K,N) int32, coin (K), normal (K)) for the K kept units, or None to draw like draw_refine from their counts under the
         builder's random_flip / random_shift.  The host reads K numbers here: the predicted widths, which decide the padded
         window counts.  ONE launch of fcn_prepare_inputs_refine.  With no kept unit the dict holds 'kept' alone."""
-        if self.device.type != "cuda":
-            raise RuntimeError("frustum_convnet_amd: input construction is a HIP kernel (MI355X only); no CPU fallback")
+        _need_device(self.device)
         kept = np.asarray(sel["kept"], dtype=np.int64)
         K = len(kept)
         if K == 0:
@@ -782,50 +664,40 @@ class RefineInputBuilder:
              "corners": sel["box3d"].reshape(K, 24), "heading": sel["heading"], "size": sel["size"],
              "coin": coin, "normal": normal}
         out = self._launch(t, K, int(sel["points"].shape[1]), self._lpad(widths), True)
-        size_class = [self.classes.index(types[i]) for i in sel["unit_cand"]]
-        out["size_class"] = torch.tensor(size_class, dtype=torch.int64).view(K, 1).to(dev, non_blocking=True)
-        if self.one_hot:
-            out["one_hot"] = self._one_hot(size_class)
+        _class_rows(self, out, [types[i] for i in sel["unit_cand"]])
         return out
 
     def build(self, records, draws=None, with_labels=True):
         """records: dicts with REFINE_KEYS (points (n,>=3) float32 rect camera coordinates; box3d (8,3), heading, size (l,w,h)
         of the label box; pred_box3d (8,3), pred_angle, pred_size of the first-stage prediction; type).  Returns the batch
         dict on the device (+ 'lens' (B,4) int32: the per-sample window counts before padding)."""
-        if self.device.type != "cuda":
-            raise RuntimeError("frustum_convnet_amd: input construction is a HIP kernel (MI355X only); no CPU fallback")
+        _need_device(self.device)
         B, N = len(records), self.npoints
         counts = [len(r["points"]) for r in records]
         if draws is None:
             draws = draw_refine(counts, N, self.random_flip and with_labels, self.random_shift and with_labels)
-        stride = int(records[0]["points"].shape[1])
-        raw = np.concatenate([np.ascontiguousarray(r["points"], dtype=np.float32) for r in records], 0)
-        off = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
-        f64 = lambda k, shape: np.stack([np.asarray(r[k], dtype=np.float64).reshape(shape) for r in records])
-        psize = f64("pred_size", (3,))
+        pt_stride = int(records[0]["points"].shape[1])
+        h = _pack(records, counts, (("pcorners", "pred_box3d", (24,)), ("pangle", "pred_angle", ()), ("psize", "pred_size", (3,))))
         # batch maxima of len(np.arange(-w/2, w/2, s)): the padded widths of the outputs
-        Lpad = self._lpad(psize[:, 1])
+        Lpad = self._lpad(h["psize"][:, 1])
         dev = self.device
-        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev, non_blocking=True)
-        t = {"raw": up(raw), "off": up(off),
-             "pcorners": up(f64("pred_box3d", (24,))), "pangle": up(f64("pred_angle", ())), "psize": up(psize)}
+        t = {k: _up(v, dev) for k, v in h.items()}
         if isinstance(draws, DeviceDraws):
             draws = draws.draw(_row_counts(t["off"]), N, self.random_flip and with_labels, self.random_shift and with_labels)
         choice, coin, normal = _draw_tensors(draws, dev, 3)
         t["choice"] = choice
         if with_labels:
-            t.update(corners=up(f64("box3d", (24,))), heading=up(f64("heading", ())), size=up(f64("size", (3,))),
-                     coin=coin, normal=normal)
-        out = self._launch(t, B, stride, Lpad, with_labels)
-        size_class = [self.classes.index(r["type"]) for r in records]
-        if with_labels:
-            out["size_class"] = torch.tensor(size_class, dtype=torch.int64).view(B, 1).to(dev, non_blocking=True)
-        if self.one_hot:
-            out["one_hot"] = self._one_hot(size_class)
+            labels = _stacks(records, (("corners", "box3d", (24,)), ("heading", "heading", ()), ("size", "size", (3,))))
+            t.update({k: _up(v, dev) for k, v in labels.items()}, coin=coin, normal=normal)
+        out = self._launch(t, B, pt_stride, Lpad, with_labels)
+        names = [r["type"] for r in records]
+        if not (with_labels or self.one_hot):
+            [self.classes.index(n) for n in names]                 # this path refuses an unknown class whatever it writes
+        _class_rows(self, out, names, size_class=with_labels)
         if not with_labels:
             # from_rgb_detection path (provider_sample_refine.py:404-419): the 2-D detector's score travels with the sample and
             # becomes the detection score's prior in detect() (train/test_net_det.py:214,279)
-            out["rgb_prob"] = up(np.asarray([float(r.get("prob", 1.0)) for r in records], dtype=np.float32).reshape(B, 1))
+            out["rgb_prob"] = _up(np.asarray([float(r.get("prob", 1.0)) for r in records], dtype=np.float32).reshape(B, 1), dev)
         return out
 
 

@@ -202,6 +202,8 @@ CASES += [
     ("test_gpu_inputs_edges", "test_refusals_leave_the_outputs_alone", ("fcn_prepare_inputs_infer",)),
     ("test_gpu_inputs_edges", "test_refusals_leave_the_outputs_alone", ("fcn_prepare_inputs_sunrgbd",)),
     ("test_gpu_inputs_edges", "test_refusals_leave_the_outputs_alone", ("fcn_prepare_inputs_refine",)),
+    ("test_gpu_inputs_edges", "test_refusals_leave_the_outputs_alone", ("fcn_prepare_inputs_sunrgbd_infer",)),
+    ("test_gpu_inputs_edges", "test_sunrgbd_infer_entry", ()),
 ]
 for _path in ("build", "build_infer", "build_device", "build_device_train"):
     CASES += [("test_gpu_inputs_edges", "test_a_sample_without_a_window_is_refused", (_path, (1.6, -0.3, 0.0), 1, "-0.3")),

@@ -1,10 +1,10 @@
-"""-m gpu: the two batch-builder kernels of csrc/inputs.hip (prepare_inputs_kernel behind fcn_prepare_inputs / _infer / _sunrgbd,
+"""-m gpu: the two batch-builder kernels of csrc/inputs.hip (prepare_inputs_kernel behind fcn_prepare_inputs / _infer / _sunrgbd / _sunrgbd_infer,
 prepare_inputs_refine_kernel behind fcn_prepare_inputs_refine) OFF their recorded fixtures: the nearest-centre fallback on the last
 real window of a padded row, one window next to many, more windows than threads (a thread's second trip, the cross-thread
 (distance, index) reduction), exact distance ties, centres exactly on a box face, both clamps of both shifts, a coin of exactly
 0.5, every flip / shift setting, SUN-RGBD without the height-shift pointer and with boxes that fall back through K and Rtilt,
 B = 1, N = 1, N below / at / above a record's point count, the inference forms of both kernels, launches into poisoned buffers,
-every refusal of the four C entries -- and RefineInputBuilder's refusal of a sample without a window.
+every refusal of the five C entries -- and RefineInputBuilder's refusal of a sample without a window.
 
 The cases (records, draws, expected batch) come from tests/inputs_cases.py; the referee is always oracle/inputs_ref.py: integer
 outputs exact, float outputs within 1e-6 * max(1, |ref|.max()) (fp64 arithmetic rounded to fp32 on both sides), the worst float
@@ -174,6 +174,8 @@ def _call(entry, case, t, out, Ls, desc=None, null=()):
                         refs] + tail + ["seg_label"]
     elif entry == "fcn_prepare_inputs_infer":
         names = head + ["choice", "fangle", "box2d", "P", "point_cloud", refs, "rot_angle"]
+    elif entry == "fcn_prepare_inputs_sunrgbd_infer":
+        names = head + ["choice", "fangle", "box2d", "K", "Rtilt", "point_cloud", refs, "rot_angle"]
     elif entry == "fcn_prepare_inputs_sunrgbd":
         names = head + ["raw_seg", "choice", "fangle", "box2d", "K", "Rtilt", "corners", "heading", "size", "coin", "normal", "hshift",
                         "point_cloud", refs] + tail + ["seg_label"]
@@ -261,22 +263,44 @@ def test_kitti_infer_entry():
     _untouched(infer, before, "fcn_prepare_inputs_infer")
 
 
+def test_sunrgbd_infer_entry():
+    """fcn_prepare_inputs_sunrgbd_infer (the kernel with corners == NULL, centres through K and Rtilt) on the SUN-RGBD fixture's
+    records equals the training entry's point_cloud, center_ref1..5 and rot_angle with flip and shift off, bit for bit -- in
+    poisoned buffers, every element written --, and refuses a descriptor that asks for flip or shift."""
+    case = ic.built("sunrgbd-f0s0-rec-n257")
+    t = _inputs(case)
+    train, Ls = _poisoned(case)
+    assert _call("fcn_prepare_inputs_sunrgbd", case, t, train, Ls) == 0
+    infer, _ = _poisoned(case, labels=False)
+    assert _call("fcn_prepare_inputs_sunrgbd_infer", case, t, infer, Ls) == 0
+    torch.cuda.synchronize()
+    assert sorted(infer) == ["center_ref1", "center_ref2", "center_ref3", "center_ref4", "center_ref5", "point_cloud", "rot_angle"]
+    for k, v in infer.items():
+        assert not bool(torch.isnan(v).any()), k
+        assert torch.equal(_bits(v), _bits(train[k])), k
+    _compare("sunrgbd_infer_entry (training entry)", train, case["want"], ic.SUNRGBD_FLOAT_KEYS, ("cls_label", "seg_label"))
+    before = _snapshot(infer)
+    assert _call("fcn_prepare_inputs_sunrgbd_infer", case, t, infer, Ls, desc=dict(random_flip=1)) == FCN_E_BADARG
+    assert _call("fcn_prepare_inputs_sunrgbd_infer", case, t, infer, Ls, desc=dict(random_shift=1)) == FCN_E_BADARG
+    _untouched(infer, before, "fcn_prepare_inputs_sunrgbd_infer")
+
+
 # ---------------------------------------------------------------------------------------------------------------- refusals
 def _refusal_case(entry):
     if entry == "fcn_prepare_inputs_refine":
         return ic.built("fallback_last_padded-on")
-    if entry == "fcn_prepare_inputs_sunrgbd":
+    if entry in ("fcn_prepare_inputs_sunrgbd", "fcn_prepare_inputs_sunrgbd_infer"):
         return ic.built("sunrgbd-f1s1-rec-n257")
     return ic.built("kitti_shift_clamps-mid")
 
 
 @pytest.mark.parametrize("entry", ["fcn_prepare_inputs", "fcn_prepare_inputs_infer", "fcn_prepare_inputs_sunrgbd",
-                                   "fcn_prepare_inputs_refine"])
+                                   "fcn_prepare_inputs_sunrgbd_infer", "fcn_prepare_inputs_refine"])
 def test_refusals_leave_the_outputs_alone(entry):
     """Every argument check of the C entry returns FCN_E_BADARG before any launch: the poisoned outputs stay as they were.  The
     unrefused call on the same tensors returns 0 (last, so that the poison is still there for the refusals)."""
     case = _refusal_case(entry)
-    infer = entry == "fcn_prepare_inputs_infer"
+    infer = entry in ("fcn_prepare_inputs_infer", "fcn_prepare_inputs_sunrgbd_infer")
     refine = entry == "fcn_prepare_inputs_refine"
     t = _inputs(case)
     out, Ls = _poisoned(case, labels=not infer)
@@ -291,8 +315,9 @@ def test_refusals_leave_the_outputs_alone(entry):
                 ("stride[%d] = 0" % s, {"stride%d" % s: 0.0}, ()), ("stride[%d] < 0" % s, {"stride%d" % s: -0.5}, ()),
                 ("stride[%d] NaN" % s, {"stride%d" % s: float("nan")}, ()), ("no center_ref%d" % (s + 1), {}, ("center_ref%d" % (s + 1),))]
     if infer:
-        bad += [("flip", dict(random_flip=1), ()), ("shift", dict(random_shift=1), ()), ("no P", {}, ("P",)),
+        bad += [("flip", dict(random_flip=1), ()), ("shift", dict(random_shift=1), ()),
                 ("no frustum_angle", {}, ("fangle",)), ("no box2d", {}, ("box2d",))]
+        bad += [("no P", {}, ("P",))] if nsc == 4 else [("no K", {}, ("K",)), ("no Rtilt", {}, ("Rtilt",))]
     else:
         bad += [("flip without coin", dict(random_flip=1), ("coin",)), ("shift without normal", dict(random_shift=1), ("normal",))]
     if refine:
