@@ -92,7 +92,7 @@ EXPORTS = ("fcn_arch", "fcn_build_hash", "fcn_stat_replicas", "fcn_query_depth_p
            "fcn_convnet_backward", "fcn_box3d_iou_pair_f32", "fcn_decode_detections", "fcn_rotate_nms_3d",
            "fcn_decode_detections_rule", "fcn_box3d_corners", "fcn_det_match", "fcn_det_ap",
            "fcn_kitti_label_rows", "fcn_kitti_overlaps", "fcn_kitti_pass_a", "fcn_kitti_thresholds", "fcn_kitti_pass_b", "fcn_kitti_curves",
-           "fcn_draw_batch", "fcn_draw_limits",
+           "fcn_draw_batch", "fcn_draw_limits", "fcn_epoch_pick", "fcn_epoch_pick_limits",
            "fcn_box2d_perturb", "fcn_box2d_perturb_limits", "fcn_frustum_train_count", "fcn_frustum_train_fill", "fcn_frustum_train_plan",
            "fcn_frustum_train_plan_limits",
            "fcn_box2d_perturb_sunrgbd", "fcn_frustum_sunrgbd_train_count", "fcn_frustum_sunrgbd_train_fill",
@@ -295,6 +295,11 @@ def lib():
         L.fcn_draw_batch.argtypes = [ctypes.POINTER(DrawDesc)] + [c_fp] * 3 + [ctypes.c_uint64] + [c_fp] * 7
         L.fcn_draw_limits.restype = ctypes.c_int
         L.fcn_draw_limits.argtypes = [ctypes.POINTER(ctypes.c_int)] * 2
+    if hasattr(L, "fcn_epoch_pick") or "FCN_LIB_NAME" not in os.environ:
+        L.fcn_epoch_pick.restype = ctypes.c_int
+        L.fcn_epoch_pick.argtypes = [c_fp] + [ctypes.c_int] * 3 + [ctypes.c_uint64, c_fp, ctypes.c_int] + [c_fp] * 3
+        L.fcn_epoch_pick_limits.restype = ctypes.c_int
+        L.fcn_epoch_pick_limits.argtypes = [ctypes.POINTER(ctypes.c_int)] * 2
     if hasattr(L, "fcn_frustum_train_plan") or "FCN_LIB_NAME" not in os.environ:
         L.fcn_box2d_perturb.restype = ctypes.c_int
         L.fcn_box2d_perturb.argtypes = [c_fp] * 3 + [ctypes.c_int] * 2 + [ctypes.c_double, ctypes.c_uint64, c_fp, ctypes.c_int] + [c_fp] * 3

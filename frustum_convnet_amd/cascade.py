@@ -203,11 +203,14 @@ class RefineTrainSource:
     padded window counts of center_ref1..4 (a unit whose predicted width needs more is dropped and flagged); seed: the three
     generators are DeviceDraws keyed seed (detection pick), seed + 1 (box jitter), seed + 2 (per-sample draws), each one step
     further after every step().  pick=False: the first D detections in order; jitter=False: A = 1 without jitter; jitter=<(D,A,7)
-    array>: that fixed table of uniforms on every step.
+    array>: that fixed table of uniforms on every step.  pick="epoch": the D detections are a rank window of the EPOCH's permutation
+    of the R rows (inputs.EpochSampler keyed seed, held as self.sampler: every row at most once per epoch, the tail of
+    R mod (D * world) dropped); rank / world, with this mode only: this rank's window among `world` sources built alike
+    (D * world <= R).  The three DeviceDraws step on as under pick=False.
     Everything is validated here, once, on the host; step() validates nothing and reads nothing."""
 
     def __init__(self, frame_points, frame_off, dets, det_frame, det_types, gt_box3d, gt_off, builder, B, D, A, capacity, lpad,
-                 seed, thresh=0.5, ratio=1.2, shift_ratio=0.05, pick=True, jitter=True):
+                 seed, thresh=0.5, ratio=1.2, shift_ratio=0.05, pick=True, jitter=True, rank=None, world=None):
         who = "RefineTrainSource"
         pts, foff, F, ps, S = _frames(who, frame_points, frame_off, resident=True)
         dev = frame_points.device
@@ -254,9 +257,10 @@ class RefineTrainSource:
             raise ValueError("%s: shift_ratio must lie in [0, 1) and ratio be positive, got %r, %r" % (who, shift_ratio, ratio))
         resident.need_device_builder(builder)
         cls = resident.class_index(who, builder.classes, types)
+        pick, self.sampler = resident.pick_mode(who, pick, rank, world, seed, builder.device, D, R, "R")
         self.device, self.builder, self.lpad = dev, builder, lpad
         self.B, self.D, self.A, self.U, self.R, self.G, self.F, self.S, self.ps, self.capacity = B, D, A, U, R, G, F, S, ps, capacity
-        self.pick, self.draw_jitter = bool(pick), fixed is None and bool(jitter)
+        self.pick, self.draw_jitter = pick, fixed is None and bool(jitter)
         self.thresh, self.ratio, self.shift_ratio = float(thresh), float(ratio), r
         f64, i32, i64 = (dict(dtype=t, device=dev) for t in (torch.float64, torch.int32, torch.int64))
         N = builder.npoints
@@ -327,10 +331,13 @@ class RefineTrainSource:
         pts, foff = self.frames
         with torch.cuda.device(dev):
             s = _native.current_stream(dev)
-            if self.pick:
+            if self.sampler is not None:
+                self.sampler.pick(self.r_count, D, out=self.cand_row)
+                self._gather_candidates()
+            elif self.pick:
                 self.draws_pick.draw(self.r_count, D, False, False, out=(self.cand_row,) + self.pick_scalars)
                 self._gather_candidates()
-            else:                                               # (the three step counters stay equal)
+            if self.sampler is not None or not self.pick:       # (the three step counters stay equal)
                 _native.check(L.fcn_box3d_jitter_draw(0, 1, self.draws_pick.seed, p(self.draws_pick.state), 1, p(self.pick_scalars[0]), s),
                               "fcn_box3d_jitter_draw")
             crow = self.cand_row.view(-1)
@@ -364,7 +371,7 @@ class RefineTrainSource:
         """Reads the status words of the plan and the three generators (a synchronisation: not for a captured region); raises
         ValueError naming the bits set since the last check() and clears them."""
         check_status("RefineTrainSource", (self.status, self.draws_pick.status, self.draws_jitter.status, self.draws_sample.status),
-                     STATUS_BITS)
+                     STATUS_BITS, self.sampler)
 
 
 # ------------------------------------------------------------------------------------------------

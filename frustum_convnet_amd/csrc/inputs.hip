@@ -461,6 +461,11 @@ extern "C" int fcn_prepare_inputs_refine(const fcn_inp_refine_desc *d, const flo
 #include "draws.h"
 
 // ------------------------------------------------------------------------------------------------
+// The training sources' labels per step as a rank window of the epoch's permutation -- every label at most once per epoch, the
+// tail dropped, 16 bytes of state -- on the draws' generator (fcn_epoch_pick, fcn_epoch_pick_limits): csrc/epoch_pick.h
+#include "epoch_pick.h"
+
+// ------------------------------------------------------------------------------------------------
 // The first stage's training input without a host read: box perturbation on the draws' stream, the labelled count / fill without
 // their read-back, and the one-workgroup plan between them (fcn_box2d_perturb, fcn_frustum_train_count / _plan / _fill):
 // csrc/frustum_plan.h

@@ -409,16 +409,26 @@ def sunrgbd_training_candidates(frame_points, frame_off, K, Rtilt, boxes2d, box_
 
 # ------------------------------------------------------------------------------------------------
 # The KITTI first stage's training input as ONE capturable sequence of launches (csrc/frustum_plan.h)
-def check_status(who, words, bits):
+def check_status(who, words, bits, sampler=None):
     """The check() of every capturable source: reads the status words (a synchronisation); where a bit is set, clears the words and
-    raises ValueError naming who and the texts of the set bits (bits: a STATUS_BITS table)."""
+    raises ValueError naming who and the texts of the set bits (bits: a STATUS_BITS table).  sampler: the source's EpochSampler or
+    None -- its word (whose bit 0 would read as the draws') is reported as EPOCH_STATUS_BIT."""
+    if sampler is not None:
+        words = tuple(words) + (sampler.status,)
+    vals = [int(v) for v in torch.cat(words).cpu().tolist()]
     s = 0
-    for v in torch.cat(words).cpu().tolist():
-        s |= int(v)
+    for v in (vals if sampler is None else vals[:-1]):
+        s |= v
+    if sampler is not None and vals[-1]:
+        s |= EPOCH_STATUS_BIT[0]
     if s:
         for w in words:
             w.zero_()
-        raise ValueError("%s: status %d -- %s" % (who, s, "; ".join(text for bit, text in bits if s & bit)))
+        raise ValueError("%s: status %d -- %s" % (who, s, "; ".join(text for bit, text in tuple(bits) + (EPOCH_STATUS_BIT,) if s & bit)))
+
+
+EPOCH_STATUS_BIT = (4096, "bit 12: the epoch sampler had no window -- a turn outside the epoch, or D * world labels exceed the table "
+                          "(its pick is zeros: label 0 repeated; its state stayed)")
 
 
 STATUS_BITS = ((1, "bit 0: a slot had no row to draw from (its choice row is zeros)"),
@@ -441,10 +451,15 @@ class FrameTrainSource:
     generators are DeviceDraws keyed seed (label pick), seed + 1 (box perturbation), seed + 2 (per-sample draws), each one step
     further after every step().  pick=False: the first D labels in order; perturb=False: the boxes as they are -- select_box2d
     (G,4) then optionally gives boxes that select in place of gt_box2d, which keeps deciding the reject rule.
+    pick="epoch": the D labels are a rank window of the EPOCH's permutation (inputs.EpochSampler keyed seed, held as self.sampler:
+    every label at most once per epoch, the tail of G mod (D * world) dropped, as the reference's shuffling loader does); rank /
+    world, with this mode only: the window of this rank among `world` sources built alike (D * world <= G).  The three DeviceDraws
+    step on as under pick=False.
     Everything is validated here, once, on the host; step() validates nothing and reads nothing."""
 
     def __init__(self, frame_points, frame_off, calib, img_size, gt_box2d, gt_box3d, box_frame, types, builder, B, D, capacity,
-                 seed, perturb=True, pick=True, shift_ratio=0.1, min_box_height=25.0, clip_distance=2.0, select_box2d=None):
+                 seed, perturb=True, pick=True, shift_ratio=0.1, min_box_height=25.0, clip_distance=2.0, select_box2d=None,
+                 rank=None, world=None):
         who = "FrameTrainSource"
         pts, foff, F, ps, S = _frames(who, frame_points, frame_off, resident=True)
         dev = frame_points.device
@@ -458,9 +473,10 @@ class FrameTrainSource:
         r = float(shift_ratio)
         if not (0.0 <= r < 1.0):
             raise ValueError("%s: shift_ratio must lie in [0, 1), got %r" % (who, shift_ratio))
+        pick, self.sampler = resident.pick_mode(who, pick, rank, world, seed, builder.device, D, G)
         self.device, self.builder = dev, builder
         self.B, self.D, self.G, self.F, self.S, self.ps, self.capacity = B, D, G, F, S, ps, capacity
-        self.perturb, self.pick, self.shift_ratio = bool(perturb), bool(pick), r
+        self.perturb, self.pick, self.shift_ratio = bool(perturb), pick, r
         self.min_box_height, self.clip_distance = float(min_box_height), float(clip_distance)
         f64, i32, i64 = (dict(dtype=t, device=dev) for t in (torch.float64, torch.int32, torch.int64))
         N = builder.npoints
@@ -511,7 +527,7 @@ class FrameTrainSource:
         pts, foff, P, V2C, R0, wh = self.frames
         with torch.cuda.device(dev):
             s = _native.current_stream(dev)
-            self.labels.pick(self.draws_pick, self.pick, self._advance_pick)
+            self.labels.pick(self.draws_pick, self.pick, self._advance_pick, self.sampler)
             _native.check(L.fcn_box2d_perturb(p(self.gt2d), p(self.bframe), p(wh), D if self.perturb else 0, self.F, self.shift_ratio,
                                               self.draws_box.seed, p(self.draws_box.state), 1, p(self.boxes), p(self.status), s),
                           "fcn_box2d_perturb")
@@ -540,7 +556,7 @@ class FrameTrainSource:
         """Reads the status words of the plan, the perturbation and the three generators (a synchronisation: not for a captured
         region); raises ValueError naming the bits set since the last check() and clears them."""
         check_status("FrameTrainSource", (self.status, self.draws_pick.status, self.draws_box.status, self.draws_sample.status),
-                     STATUS_BITS)
+                     STATUS_BITS, self.sampler)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -559,6 +575,7 @@ class SunrgbdTrainSource:
     boxes that select; sub (with perturb=False and pick=False): one entry per first-D label, the subsample of that label's frustum
     (indices into its selected rows) or None, in place of the device's draw -- range-checked here against the counts of one count
     launch, and refused when `capacity` cannot hold every row (an index must never point at a row that was not stored).
+    pick="epoch", rank, world: as FrameTrainSource takes them -- a rank window of the epoch's permutation (self.sampler).
     ALL pre-kept boxes (full positives >= min_positives) are filled, not only the B that end up holding a slot: the slots are decided
     after the subsample, which needs the labels of the stored rows.  So `capacity` has to hold the rows of up to D frustums:
     D times the longest frame is a sure bound; a smaller buffer works as long as check() does not report bit 2 -- rows beyond it are
@@ -566,7 +583,8 @@ class SunrgbdTrainSource:
     Everything is validated here, once, on the host; step() validates nothing, allocates nothing, reads nothing and uploads nothing."""
 
     def __init__(self, frame_points, frame_off, K, Rtilt, gt_box2d, gt_box3d, box_frame, types, builder, B, D, capacity, seed,
-                 perturb=True, pick=True, shift_ratio=0.1, cap=SUNRGBD_CAP, min_positives=SUNRGBD_MIN, select_box2d=None, sub=None):
+                 perturb=True, pick=True, shift_ratio=0.1, cap=SUNRGBD_CAP, min_positives=SUNRGBD_MIN, select_box2d=None, sub=None,
+                 rank=None, world=None):
         who = "SunrgbdTrainSource"
         pts, foff, F, ps, S = _frames(who, frame_points, frame_off, resident=True)
         dev = frame_points.device
@@ -585,9 +603,10 @@ class SunrgbdTrainSource:
             raise ValueError("%s: shift_ratio must lie in [0, 1), got %r" % (who, shift_ratio))
         if sub is not None and (perturb or pick) and not (perturb and select_box2d is not None):   # (that refusal of load() comes first)
             raise ValueError("%s: sub goes with perturb=False and pick=False" % who)
+        pick, self.sampler = resident.pick_mode(who, pick, rank, world, seed, builder.device, D, G)
         self.device, self.builder = dev, builder
         self.B, self.D, self.G, self.F, self.S, self.ps, self.capacity = B, D, G, F, S, ps, capacity
-        self.perturb, self.pick, self.shift_ratio, self.cap, self.min_positives = bool(perturb), bool(pick), r, cap, min_positives
+        self.perturb, self.pick, self.shift_ratio, self.cap, self.min_positives = bool(perturb), pick, r, cap, min_positives
         f64, i32, i64 = (dict(dtype=t, device=dev) for t in (torch.float64, torch.int32, torch.int64))
         N = builder.npoints
         # ---- resident: the frames, the label table (no clip: nothing of the boxes to refuse), the generators
@@ -665,7 +684,7 @@ class SunrgbdTrainSource:
         p = lambda x: x.data_ptr()
         with torch.cuda.device(dev):
             s = _native.current_stream(dev)
-            self.labels.pick(self.draws_pick, self.pick, self._advance_pick)
+            self.labels.pick(self.draws_pick, self.pick, self._advance_pick, self.sampler)
             _native.check(L.fcn_box2d_perturb_sunrgbd(p(self.gt2d), D if self.perturb else 0, self.shift_ratio, self.draws_box.seed,
                                                       p(self.draws_box.state), 1, p(self.boxes), s), "fcn_box2d_perturb_sunrgbd")
             args = self._args()
@@ -707,7 +726,7 @@ class SunrgbdTrainSource:
         """Reads the status words of the plan, the slots and the four generators (a synchronisation: not for a captured region);
         raises ValueError naming the bits set since the last check() and clears them."""
         check_status("SunrgbdTrainSource", (self.status, self.draws_pick.status, self.draws_box.status, self.draws_sample.status,
-                                            self.draws_sub.status), STATUS_BITS)
+                                            self.draws_sub.status), STATUS_BITS, self.sampler)
 
 
 # ------------------------------------------------------------------------------------------------

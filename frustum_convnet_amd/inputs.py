@@ -9,6 +9,8 @@ By default randomness stays on the host and follows the reference's call order p
 np.random.random (flip coin), np.random.randn (depth shift) -- so with the same numpy seed the batch equals the
 reference's batch (tests/test_gpu_inputs.py checks that against the golden fixture).  DeviceDraws makes the same draws on the
 device from a counter-based stream of its own (C-ABI fcn_draw_batch, csrc/draws.h): every builder takes one as `draws=`.
+EpochSampler picks a training step's labels from the same stream as a rank window of the epoch's permutation (C-ABI fcn_epoch_pick,
+csrc/epoch_pick.h): what the training sources' pick="epoch" runs.
 """
 import ctypes
 
@@ -112,6 +114,77 @@ class DeviceDraws:
         if s:
             self.status.zero_()
             raise ValueError("DeviceDraws: a sample had no row to draw from (or 2^31 rows or more): its choice row is zeros")
+
+
+class EpochSampler:
+    """The labels of a training step as a rank window of the EPOCH's permutation, on the device (C-ABI fcn_epoch_pick,
+    csrc/epoch_pick.h): what the reference's DataLoader(shuffle=True, drop_last=True) walks -- a fresh permutation per epoch, every
+    label at most once per epoch, the tail that fills no step dropped -- with no G-sized table and no host read, capturable
+    (INTEGRATION.md "Epoch-exact label sampling" states the contract bit for bit).  The permutation of epoch e is the order
+    DeviceDraws gives row 0 at step e under the same `seed`; a step takes the D labels at ranks (turn * world + rank) * D ...
+    state: (2,) int64 -- epoch, turn; every pick() reads it and leaves the next turn (or the next epoch's turn 0) behind, in stream
+    order; writing a pair back reproduces that pick, so a checkpoint of the data order is these 16 bytes.  Ranks built with the same
+    seed hold the same state and take disjoint windows.  status: (1,) int32 -- bit 0 is set by a pick that had no window (see
+    check())."""
+
+    def __init__(self, seed, device="cuda", rank=0, world=1):
+        self.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError("frustum_convnet_amd: the epoch sampler is a HIP kernel (MI355X only); no CPU fallback")
+        self.rank, self.world = int(rank), int(world)
+        if self.world < 1 or not (0 <= self.rank < self.world):
+            raise ValueError("EpochSampler: need world >= 1 and 0 <= rank < world, got rank = %d, world = %d" % (self.rank, self.world))
+        self.state = torch.zeros((2,), dtype=torch.int64, device=self.device)
+        self.status = torch.zeros((1,), dtype=torch.int32, device=self.device)
+
+    @staticmethod
+    def limits():
+        """(the largest D, the count up to which the permutation is sorted whole in LDS) of fcn_epoch_pick."""
+        a, b = ctypes.c_int(0), ctypes.c_int(0)
+        _native.check(_native.lib().fcn_epoch_pick_limits(ctypes.byref(a), ctypes.byref(b)), "fcn_epoch_pick_limits")
+        return a.value, b.value
+
+    def steps_per_epoch(self, G, D):
+        """The turns of an epoch over G labels at D per step and rank: floor(G / (D * world))."""
+        return int(G) // (int(D) * self.world)
+
+    @staticmethod
+    def _want(name, t, dtype, numel):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise ValueError("EpochSampler.pick: %s must be a device tensor" % name)
+        if t.dtype != dtype or not t.is_contiguous():
+            raise ValueError("EpochSampler.pick: %s must be a contiguous %s tensor, got %s" % (name, dtype, t.dtype))
+        if t.numel() != numel:
+            raise ValueError("EpochSampler.pick: %s must hold %d elements, got %s" % (name, numel, tuple(t.shape)))
+        return t
+
+    def pick(self, count, D, out=None, advance=True):
+        """count (1,) int64 on the device: the number of labels G.  -> pick (D,) int32 on the device, into `out` (D elements) when
+        given: then there is no allocation and no host read, only the launch -- capturable.  A state without a window (D * world > G,
+        a turn outside the epoch, G outside (0, 2^31)) gives zeros, flags `status` and stays as it was: see check()."""
+        D = int(D)
+        self._want("count", count, torch.int64, 1)
+        if D <= 0:
+            raise ValueError("EpochSampler.pick: %d labels per step" % D)
+        if out is None:
+            out = torch.empty((D,), dtype=torch.int32, device=self.device)
+        self._want("out", out, torch.int32, D)
+        with torch.cuda.device(self.device):
+            _native.check(_native.lib().fcn_epoch_pick(count.data_ptr(), D, self.rank, self.world, self.seed, self.state.data_ptr(),
+                                                       1 if advance else 0, out.data_ptr(), self.status.data_ptr(),
+                                                       _native.current_stream(self.device)), "fcn_epoch_pick")
+        count.record_stream(torch.cuda.current_stream(self.device))
+        return out
+
+    def check(self):
+        """Reads `status` (a synchronisation: not for a captured region) and raises ValueError when a pick since the last check()
+        had no window; the word is cleared."""
+        s = int(self.status.cpu()[0])
+        if s:
+            self.status.zero_()
+            raise ValueError("EpochSampler: a pick had no window (D * world > G, a turn outside the epoch, or G outside (0, 2^31)): "
+                             "it is zeros and the state stayed")
 
 
 def _is_device_draws(draws):

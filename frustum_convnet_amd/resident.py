@@ -79,6 +79,25 @@ def check_slots(who, B, D, max_d, G=None, b="B"):
         raise ValueError("%s: need 1 <= B <= D <= G and D <= %d, got B = %d, D = %d, G = %d" % (who, max_d, B, D, G))
 
 
+def pick_mode(who, pick, rank, world, seed, dev, D, G, g="G"):
+    """A training source's `pick` option -> (the value it stores, its EpochSampler or None).  True: D of the G labels drawn anew
+    every step; False: the first D in order; "epoch": a rank window of the epoch's permutation (inputs.EpochSampler keyed `seed`),
+    the only mode rank / world go with -- there D * world <= G; g: what the source calls G."""
+    if isinstance(pick, str):                                   # (bool("epoch") is True: the string is tested first)
+        if pick != "epoch":
+            raise ValueError("%s: pick must be True, False or \"epoch\", got %r" % (who, pick))
+        rank, world = 0 if rank is None else int(rank), 1 if world is None else int(world)
+        if world < 1 or not (0 <= rank < world):
+            raise ValueError("%s: need world >= 1 and 0 <= rank < world, got rank = %d, world = %d" % (who, rank, world))
+        if D * world > G:
+            raise ValueError("%s: pick=\"epoch\" needs D * world <= %s, got D = %d, world = %d, %s = %d" % (who, g, D, world, g, G))
+        from .inputs import EpochSampler
+        return "epoch", EpochSampler(seed, dev, rank, world)
+    if rank is not None or world is not None:
+        raise ValueError("%s: rank and world go with pick=\"epoch\"" % who)
+    return bool(pick), None
+
+
 def check_segments(who, D, S, max_segs):
     if D * S > max_segs:
         raise ValueError("%s: D * S = %d * %d segments exceed the plan's %d" % (who, D, S, max_segs))
@@ -183,10 +202,15 @@ class LabelTable:
         for src, dst in ((self.g_box2d, self.gt2d), (self.g_sel2d, self.sel2d), (self.g_box3d, self.gt3d), (self.g_frame, self.bframe)):
             torch.index_select(src, 0, idx, out=dst)
 
-    def pick(self, draws, drawn, advance):
+    def pick(self, draws, drawn, advance, sampler=None):
         """The step's D labels: drawn by draws (a DeviceDraws) and gathered, or -- not drawn: the first D in order, gathered once by
-        the source -- advance(), the dataset's launch that moves the generator one step on without drawing."""
-        if drawn:
+        the source -- advance(), the dataset's launch that moves the generator one step on without drawing.  With a sampler (an
+        EpochSampler): its window of the epoch's permutation, gathered, and advance() as well."""
+        if sampler is not None:
+            sampler.pick(self.g_count, self.D, out=self.pick_idx)
+            self._gather_labels()
+            advance()
+        elif drawn:
             draws.draw(self.g_count, self.D, False, False, out=(self.pick_idx,) + self.pick_scalars)
             self._gather_labels()
         else:

@@ -693,6 +693,26 @@ int fcn_draw_batch(const fcn_draw_desc *d, const int64_t *counts, const int32_t 
 int fcn_draw_limits(int *max_n, int *sort_cap);
 
 /* ---------------------------------------------------------------------------------------------
+ * Epoch-exact label sampling on the device (csrc/epoch_pick.h): the D labels of a training step as a rank window of the epoch's
+ * permutation, which is what the reference's DataLoader(shuffle=True, drop_last=True) walks (train/train_net_det.py:262-269).
+ * The contract, bit for bit (INTEGRATION.md "Epoch-exact label sampling"; tests/draws_ref.choice_row(seed, e, 0, G, G) is perm_e):
+ *   perm_e = the j of the G composites (k_j << 32) | j in ascending order, k_j = word j & 3 of Philox4x32-10 block j >> 2 at
+ *   counter (block, 0, e lo, ((e >> 32) << 2) | 0), key (seed lo, seed hi): fcn_draw_batch's tag-0 order of row 0 at step e.
+ *   pick[i] = perm_e[(t * world + rank) * D + i], i < D, with (e, t) = (state[0], state[1]) and G = count[0].
+ *   T = G / (D * world) turns per epoch (integer division; the tail of G - T * D * world labels is dropped for that epoch).
+ *   advance != 0: the state left behind is (e, t + 1) if t + 1 < T, else (e + 1, 0) -- stored in stream order behind every read
+ *   of it, inside the one launch (one workgroup, behind a barrier), so a replayed capture moves on and writing the state back
+ *   reproduces a pick.  Ranks with the same seed hold the same state and take disjoint windows.
+ * count (1) int64, state (2) int64, pick (D) int32, status (1) int32: device.  G <= 0, G >= 2^31, D * world > G, e < 0, t < 0 or
+ * t >= T: pick is all zeros, bit 0 of *status is set (never cleared here) and the state stays as it was; nothing is dereferenced
+ * out of range.  Capturable: no allocation, no host read.  A NULL pointer, D < 1, world < 1 or rank outside [0, world):
+ * FCN_E_BADARG; D > 2048: FCN_E_LIMIT; nothing is written. */
+int fcn_epoch_pick(const int64_t *count, int D, int rank, int world, uint64_t seed, int64_t *state, int advance, int32_t *pick,
+                   int32_t *status, void *stream);
+/* The largest D of fcn_epoch_pick and the G up to which the permutation is sorted whole in LDS (above it: rank-window select). */
+int fcn_epoch_pick_limits(int *max_d, int *sort_cap);
+
+/* ---------------------------------------------------------------------------------------------
  * The link between the two stages of the cascade: first-stage detections -> the raw points of the refinement stage.  Replaces
  * the host loop of kitti/prepare_data_refine.py::extract_frustum_data_rgb_detection (:649-773): enlarge every predicted box by
  * `ratio` (1.2 there), keep the frame's points inside it (scipy.spatial.Delaunay(...).find_simplex), pickle them for
